@@ -5,7 +5,10 @@ Contract: `python bench.py --gpus N --steps K --warmup W`.  N > 1: one rank per 
 launches the ranks (torch.distributed.run sets RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*) or, when WORLD_SIZE is unset,
 this script re-executes itself under torch.distributed.run with N ranks (the analogue of codes/train.py:19-26).
 W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + torch.cuda.synchronize() on both sides; max over
-ranks; rank 0 prints ONE JSON line.
+ranks; rank 0 prints ONE JSON line.  Every step starts from the state after setup (parameters and Adam state put back in front of it), so
+all steps do the same work on the same inputs, run after run.  A plain run does only that: set up, warm up, time, print (`--dump-outputs DIR`: and write what the
+last timed step computed, see dump_outputs).  `--full` adds, after the timed region, everything listed under "Extra objects" below
+(`--config 5` prints its own line, which is the same with or without it).
 
 Workload = BASELINE.json configs[1] ("EDVR-M 64ch, 5-frame 180x320 LR, batch 8, fwd+bwd on 1xMI355X"):
 EDVR(nf=64, nframes=5, groups=8, front_RBs=5, back_RBs=10, w_TSA=True), x4 output, driven through the package's
@@ -17,12 +20,12 @@ Synthetic data: x ~ U[0,1) seed 1234, GT ~ U[0,1) seed 1235, defa
 conv_offset_mask.weight ~ N(0, 0.01^2).  With that init alone the deformable offsets are ~0.004 px, which flatters the
 gather (SURVEY.md 8d asks for O(1) px), so by DEFAULT the offset rows of every conv_offset_mask are rescaled until the mean
 |offset| of each DCN is 1 px (`--offset-px P` for another value, `--offset-px 0` keeps the raw init; i.i.d. per pixel, i.e.
-harsher than a trained, spatially smooth field); the line reports the measured offset statistics, and `offset_sweep`
+harsher than a trained, spatially smooth field); the --full line reports the measured offset statistics, and its `offset_sweep`
 carries the raw-init (~0 px) and 3 px steps.  Weak scaling: every rank processes its own B windows; value = N*B*K / time.
 `--config {2,3,5}` selects a BASELINE.json configuration: 2 (default) = EDVR-M nf64 / 5 frames / B 8; 3 = nf128 / 7 frames /
 B 16 (per GPU: with --gpus 8 this is BASELINE config 4); 5 = 540x960 sliding-window inference (fwd only, replicas).
 
-Extra objects on the line:
+Extra objects on the line (with --full only):
   roofline     -- the fused DCN forward kernel (the kernel north_star grades): algorithmic bytes 4*(C+216+Co) per
                   output pixel summed over the timed DCN launches / their HIP-event durations, vs the
                   8 TB/s HBM3E peak.  `traffic`: HBM bytes per launch from PMC counters -- measured in this run when rocprofv3 is on
@@ -730,6 +733,35 @@ def dry_run_plan(args):
                       '--config %d --gpus %d' % (world, args.config, world)}
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of a larger dumped array (16 MB in f32): two such arrays + the loss terms stay below 64 MB
+
+
+def dump_sample(t, seed):
+    """`t` flattened to f32 on the host; above DUMP_SAMPLE elements a fixed, seeded sample of them (ascending positions)."""
+    t = t.detach().reshape(-1).float()
+    if t.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE].sort().values
+        t = t[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(model, d):
+    """`--dump-outputs DIR`: what the last timed optimize_parameters() computed, as DIR/<name>.npy -- `output` (netG's output, fake_H),
+    `grads` (the gradient of every parameter, concatenated in named_parameters() order; f32, both sampled by dump_sample above 4 M
+    elements) and one f64 scalar per loss term (l_pix, l_pix_y, l_pix_c).  Not the updated parameters: Adam moves a parameter whose
+    gradient sits at the level of the DCN input gradient's atomic-order noise by +-lr, so they would differ from run to run by more
+    than rounding while everything they come from agrees."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    params = [p for _, p in model.netG.named_parameters()]
+    arrays = {'output': dump_sample(model.fake_H, 1),
+              'grads': dump_sample(torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1) for p in params]), 3)}
+    for k, v in model.loss_terms.items():
+        arrays[k] = np.array([float(v.item())], dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+
+
 def relaunch(args):
     """`python bench.py --gpus N` without a launcher: spawn the N ranks ourselves."""
     s = socket.socket()
@@ -764,6 +796,12 @@ def main():
     ap.add_argument('--dry-run', action='store_true', help='N > 1: check launcher env, device count and backend, then exit')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-sweep', action='store_true', help='skip the post-run offset sweep and the f32-mode step')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure and check everything else: the DCN / LDS / conv rooflines, the offset sweep, the '
+                         'f32 and speed-mode steps, the CPU baseline with its parity check, the config-3 / config-5 side lines and the live '
+                         'PMC traffic pass (the --no-* options thin this out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (network output, loss terms, parameter gradients) as DIR/<name>.npy')
     ap.add_argument('--force-allreduce', action='store_true',
                     help='N = 1: initialise a one-rank RCCL process group and run the bucketed gradient all-reduce (hooks, one async '
                          'all_reduce per bucket, finish) inside every step -- arithmetically the identity, but it loads librccl and '
@@ -774,6 +812,8 @@ def main():
     elif pre.config == 5:
         ap.set_defaults(nf=128, nframes=7, batch=1, height=540, width=960)
     args = ap.parse_args()
+    if args.dump_outputs and args.config == 5:
+        ap.error('--dump-outputs covers the training configurations (--config 2 / 3)')
     if args.offset_px is not None and args.offset_px <= 0:
         args.offset_px = None
 
@@ -878,21 +918,31 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    # Every warm-up and timed step trains from this state (parameters + Adam moments and step counts put back in front of it): all steps do
+    # the same work on the same inputs, in every run.  (Chained steps would not: the DCN input gradient is an f32 atomic scatter whose last
+    # bits vary from run to run, and Adam turns a gradient element at that noise level into a +-lr move of its parameter.)
+    start = _Snapshot(model)
     for i in range(args.warmup):
+        start.restore()
         model.optimize_parameters(i + 1, log=False)
-    off = offset_stats(model.netG, x) if rank == 0 else {}
+    off = offset_stats(model.netG, x) if rank == 0 and args.full else {}
     if model.reducer is not None:
         model.reducer.reset_stats()
-    timer = DcnTimer()
-    timer.install()
+    timer = DcnTimer() if args.full else None   # per-launch HIP events of the fused DCN: the roofline objects of --full
+    if timer is not None:
+        timer.install()
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        start.restore()
         model.optimize_parameters(args.warmup + i + 1, log=False)
     fence()
     dt = time.perf_counter() - t0
-    timer.uninstall()
+    if timer is not None:
+        timer.uninstall()
     loss = model.loss_terms['l_pix']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     allreduce = None
     if use_pg:
         # every rank must hold bit-identical parameters after the last step (same averaged gradients, same Adam arithmetic)
@@ -913,22 +963,7 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
-    nl, kms, kbytes = timer.result()
-    # HBM traffic of the DCN forward kernel: NOT measured here.  PMC passes (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3
-    # runs) are kept under profiles/; their bytes per output pixel are rescaled to the pixels an average timed launch covers.
-    traffic, traffic_source = None, None   # (roofline.traffic_basis: 'micro' = PMC passes of tools/dcn_micro.py in this run, 'profile record' = the file under profiles/)
-    try:
-        with open(os.path.join(ROOT, PMC_PROFILE[args.nf])) as f:
-            pmc = json.load(f)
-        if nl > 0:
-            traffic = round(pmc['hbm_bytes_per_pixel'] * (kbytes / nl) / pmc['algorithmic_bytes_per_pixel'])
-            traffic_source = '%s (offline PMC pass at offset std %s px, rescaled to this launch size; not measured in this run)' \
-                % (PMC_PROFILE[args.nf], pmc['shape'].get('offset_std_px'))
-    except (OSError, KeyError, ValueError):
-        pass
-
     if rank == 0:
-        l1 = off.get('pcd_align.L1_dcnpack', (None, None))
         lf = "LapPyr(ssim,cb)" if args.lf_mode == 'ssim' else "LapPyr(cb,cb)"
         line = {
             'metric': 'HR frames/sec (fwd+bwd) on %d-frame %dx%d LR windows' % (N, H, W),
@@ -950,16 +985,32 @@ def main():
                        'per_gpu_batch': B, 'global_batch': world * B, 'parallelism': 'sequence-dp%d' % world,
                        'gemm': gemm_mode + GEMM_DESC[gemm_mode],
                        'lf_term': 'ssim (restated IQA_pytorch.SSIM, parity unpinned)' if args.lf_mode == 'ssim' else 'cb',
-                       'offset_abs_mean_px': None if l1[0] is None else round(l1[0], 4),
-                       'offset_abs_max_px': None if l1[1] is None else round(l1[1], 3),
-                       'offset_abs_mean_px_per_dcn': {k.split('.')[-1]: round(v[0], 4) for k, v in off.items()},
                        'offset_px_requested': args.offset_px,
                        'loss_last_step': round(float(loss.item()), 6)},
-            'roofline': dict(dcn_roofline('dcn_fwd3_kernel (+ its weight pre-pack), fused DCN forward', args.nf, args.nf, gemm_mode, timer),
-                             traffic=traffic, traffic_source=traffic_source, traffic_basis=None if traffic is None else 'profile record',
-
-                             dcn_bwd_ms_per_step=round(timer.backward_ms() / max(args.steps, 1), 3)),
         }
+        if allreduce is not None:
+            line['allreduce'] = allreduce
+    if rank == 0 and args.full:
+        l1 = off.get('pcd_align.L1_dcnpack', (None, None))
+        line['config'].update({'offset_abs_mean_px': None if l1[0] is None else round(l1[0], 4),
+                               'offset_abs_max_px': None if l1[1] is None else round(l1[1], 3),
+                               'offset_abs_mean_px_per_dcn': {k.split('.')[-1]: round(v[0], 4) for k, v in off.items()}})
+        nl, kms, kbytes = timer.result()
+        # HBM traffic of the DCN forward kernel: NOT measured here.  PMC passes (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3
+        # runs) are kept under profiles/; their bytes per output pixel are rescaled to the pixels an average timed launch covers.
+        traffic, traffic_source = None, None   # (roofline.traffic_basis: 'micro' = PMC passes of tools/dcn_micro.py in this run, 'profile record' = the file under profiles/)
+        try:
+            with open(os.path.join(ROOT, PMC_PROFILE[args.nf])) as f:
+                pmc = json.load(f)
+            if nl > 0:
+                traffic = round(pmc['hbm_bytes_per_pixel'] * (kbytes / nl) / pmc['algorithmic_bytes_per_pixel'])
+                traffic_source = '%s (offline PMC pass at offset std %s px, rescaled to this launch size; not measured in this run)' \
+                    % (PMC_PROFILE[args.nf], pmc['shape'].get('offset_std_px'))
+        except (OSError, KeyError, ValueError):
+            pass
+        line['roofline'] = dict(dcn_roofline('dcn_fwd3_kernel (+ its weight pre-pack), fused DCN forward', args.nf, args.nf, gemm_mode, timer),
+                                traffic=traffic, traffic_source=traffic_source, traffic_basis=None if traffic is None else 'profile record',
+                                dcn_bwd_ms_per_step=round(timer.backward_ms() / max(args.steps, 1), 3))
         if kms > 0:
             # what the fused DCN forward is actually bound by (profiles/r04_notes.md): not HBM -- its traffic is 1.12x the algorithmic bytes --
             # but what one pixel costs on chip.  The LDS side of that: gather + weight-fragment bytes vs the measured 146 B/clk/CU x 256 CUs x 2.4 GHz;
@@ -973,8 +1024,6 @@ def main():
                                     'frac': round(lds_ach / lds_peak, 4), 'bytes_per_pixel': round(timer.lds_bytes / max(kbytes, 1) * 4.0 * (args.nf + 216 + args.nf)),
                                     'note': 'conflict-free LDS bytes of the formulation (corner gather + weight fragments) over the timed launches; '
                                             'measured bank conflicts multiply the LDS cycles by ~1.7 (profiles/r03_dcn_sq_counters.json)'}
-        if allreduce is not None:
-            line['allreduce'] = allreduce
         line['roofline_conv'] = conv_roofline(model.netG, B * N, args.nf, H, W, gemm_mode, sustained=not args.no_sweep)
         if world == 1 and not args.no_sweep:
             nxt = args.warmup + args.steps + 1
@@ -1031,6 +1080,7 @@ def main():
                 line['roofline']['traffic_basis'] = 'micro'   # counters of tools/dcn_micro.py (same kernel, L1 shape), rescaled -- not of the timed launches
             elif line['roofline'].get('traffic_source') is not None:
                 line['roofline']['traffic_source'] += '; live PMC pass unavailable: ' + note
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if use_pg:
         torch.distributed.destroy_process_group()

@@ -4,6 +4,7 @@ itself in a one-rank group with the reducer's hook path forced on (`BucketedGrad
   * the real EDVR training step through VideoSRModel(dist) -> FlatAdam buffers -> BucketedGradAllReduce hooks on the
     custom autograd Functions: averaged gradients == full-batch gradients, ranks end with identical parameters
   * `python bench.py --gpus 2` with WORLD_SIZE unset spawns its own ranks and reports n_gpus = 2
+  * a plain `bench.py` run prints the headline only and `--dump-outputs` writes what its last timed step computed
 """
 import json
 import os
@@ -222,7 +223,8 @@ def test_bench_self_launches_n_ranks():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '1',
-                          '--height', '32', '--width', '48', '--no-cpu-baseline', '--no-extra'], env=env, capture_output=True, text=True, timeout=900)
+                          '--height', '32', '--width', '48', '--full', '--no-cpu-baseline', '--no-extra'], env=env, capture_output=True, text=True,
+                         timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
     rec = json.loads(line)
@@ -241,7 +243,7 @@ def test_bench_line_carries_offset_sweep_and_f32_step():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--batch', '1',
-                          '--height', '32', '--width', '48', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                          '--height', '32', '--width', '48', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
     assert abs(rec['config']['offset_abs_mean_px'] - 1.0) < 0.2 and rec['config']['offset_px_requested'] == 1.0
@@ -256,3 +258,44 @@ def test_bench_line_carries_offset_sweep_and_f32_step():
     assert rec['extra']['config3']['ms_per_step'] > 0 and rec['extra']['config5']['ms_per_frame'] > 0 and rec['extra']['config5']['graph_bit_identical']
     assert rec['f32_mode_ms_per_step'] > 0 and rec['roofline']['dcn_bwd_ms_per_step'] > 0
     assert 'allreduce' not in rec
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W` run: the headline line of exactly K timed steps, none of the --full objects; `--dump-outputs DIR`
+    writes the last timed step's output, loss terms and parameter gradients -- and a second run with the same arguments writes the same
+    arrays (every step starts from the same state: same inputs, so the same results up to the rounding of the DCN input gradient's atomics)."""
+    import numpy as np
+    from realvsr_amd.archs.EDVR_arch import EDVR
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        env.pop(k, None)
+    runs = []
+    for tag in ('a', 'b'):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '1',
+                              '--height', '32', '--width', '48', '--dump-outputs', str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+        assert sorted(os.listdir(d)) == ['grads.npy', 'l_pix.npy', 'l_pix_c.npy', 'l_pix_y.npy', 'output.npy']
+        runs.append((rec, {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}))
+    rec, arrs = runs[0]
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['n_gpus'] == 1 and rec['higher_is_better'] is True
+    assert rec['unit'] == 'HR frames/s' and rec['dtype'].startswith('f32') and rec['metric'].startswith('HR frames/sec')
+    assert rec['ms_per_step'] > 0 and abs(rec['value'] * rec['ms_per_step'] / 1e3 - 1.0) < 1e-2   # value = B / (ms_per_step / 1e3), B = 1
+    assert not {'roofline', 'roofline_lds', 'roofline_conv', 'offset_sweep', 'f32_mode_ms_per_step', 'speed_modes', 'cpu_baseline', 'parity',
+                'extra', 'allreduce'} & set(rec)
+    assert sum(a.nbytes for a in arrs.values()) < 64 * 2 ** 20
+    nparam = sum(p.numel() for p in EDVR(nf=64, nc=3, nframes=5, groups=8, front_RBs=5, back_RBs=10, w_TSA=True).parameters())
+    assert arrs['output'].dtype == np.float32 and arrs['output'].shape == (1 * 3 * 128 * 192,)
+    assert arrs['grads'].dtype == np.float32 and arrs['grads'].shape == (nparam,)
+    assert all(np.isfinite(a).all() for a in arrs.values()) and np.abs(arrs['grads']).max() > 0
+    for k in ('l_pix', 'l_pix_y', 'l_pix_c'):
+        assert arrs[k].dtype == np.float64 and arrs[k].shape == (1,)
+    assert abs(arrs['l_pix'][0] - (arrs['l_pix_y'][0] + arrs['l_pix_c'][0])) <= 1e-6 * abs(arrs['l_pix'][0])
+    assert abs(arrs['l_pix'][0] - rec['config']['loss_last_step']) <= 1e-6
+    # run to run: the forward is deterministic, the gradients carry the rounding of the atomic scatter only
+    other = runs[1][1]
+    for k in ('output', 'l_pix', 'l_pix_y', 'l_pix_c'):
+        assert np.array_equal(arrs[k], other[k]), k
+    g, h = arrs['grads'].astype(np.float64), other['grads'].astype(np.float64)
+    assert np.abs(g - h).max() <= 1e-5 * np.abs(h).max() and np.linalg.norm(g - h) <= 1e-5 * np.linalg.norm(h)

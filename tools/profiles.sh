@@ -6,13 +6,13 @@
 R=${1:-r06}
 O=gpurun_out/${R}_profiles; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --config 3 --steps 3 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/bench_c3.json 2>/dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --config 3 --steps 3 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/bench_c3.json 2>/dev/null
 python bench.py --config 5 > $O/infer_c5.json 2>/dev/null
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-sweep --no-extra --force-allreduce > $O/bench_force_allreduce.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/prof_default.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-sweep --no-extra --force-allreduce > $O/bench_force_allreduce.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/prof_default.json 2>/dev/null
 cp "$(find $O/prof_default -name '*kernel_stats.csv' | head -1)" $O/default_kernel_stats.csv; rm -rf $O/prof_default
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -- python bench.py --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/prof_c3.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -- python bench.py --full --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-sweep --no-extra > $O/prof_c3.json 2>/dev/null
 cp "$(find $O/prof_c3 -name '*kernel_stats.csv' | head -1)" $O/c3_kernel_stats.csv; rm -rf $O/prof_c3
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT"
 P2="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU"
