@@ -224,7 +224,9 @@ int rvsr_deform_conv_generic_backward(int dtype, const void* input, const void* 
  *        gradient then need no mask.  Built for the 8 x 64-tile kernel only: returns RVSR_ERR_UNSUPPORTED (without an error message) for
  *        frames that kernel does not take, and the caller applies the mask on the consumer side (xact / gout_act) instead.
  *   pixel_shuffle 1: out1 is (B,Co/4,2*Hout,2*Wout), written through PixelShuffle(2).
- *   stride 2 only with ksize 3 and in_mode 0.
+ *   stride 2 only with ksize 3 or 5 and in_mode 0.
+ *   ksize 5 (pad 2; the patch discriminator, discriminator_arch.py:46-92): exact-f32 kernels in every GEMM mode (no packed image,
+ *   workspace bytes 0, rvsr_conv2d_pack_weights returns 0); stride-2 data gradients through in_mode 1 as for 3x3.
  *   workspace: rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1+Co2, ksize) bytes (holds the weights
  *   re-packed as bf16 hi/lo for the matrix cores; unused in exact-f32 mode).
  *   Sizes: the fast kernels address one batch element of a tensor with 32-bit byte offsets (raw
@@ -258,7 +260,8 @@ int rvsr_pack_weights_batched(const void* descs, int n, void* stream);
  *   gout: gradient w.r.t. the conv output.  g_mode 0: stored (B,Co,Gs_h,Gs_w) = (.., Hout, Wout);
  *         g_mode 2: stored (B,Co/4,Gs_h,Gs_w) pixel-shuffled (2*Hout, 2*Wout).
  *   gact/gact_slope: fused activation derivative (stored like gout), or NULL.
- *   accumulate 0: overwrite, 1: += .  Deterministic (fixed-order reduction of partials). */
+ *   accumulate 0: overwrite, 1: += .  Deterministic (fixed-order reduction of partials).
+ *   ksize 5 (stride 1 or 2): exact-f32 kernel in every GEMM mode. */
 size_t rvsr_conv2d_wgrad_workspace_bytes(int C1, int C2, int Co, int B, int ksize, int stride, int Hout, int Wout);
 int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
                                 const float* gout, const float* gact, float gact_slope, int g_mode,
@@ -400,6 +403,38 @@ int rvsr_augment_clips(const float* im1, const float* im2, float* out1, float* o
  * and its adjoint gb[j] = sum_n gout[n][j] * act'(out[n][j]) (out NULL: no activation). */
 int rvsr_bcast_add_act(float* a, const float* b, size_t per, int N, int act, float slope, void* stream);
 int rvsr_bcast_reduce_act(const float* gout, const float* out, float* gb, size_t per, int N, float gslope, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * 7. GAN discriminator (VideoSRGAN_AllPair_model_YCbCr_Split.py; discriminator_arch.py:46-92, loss.py:102-133)
+ * --------------------------------------------------------------------------------------------- */
+
+/* nn.BatchNorm2d followed by LeakyReLU(slope) on x (B,C,HW planes), one fused operator:
+ *   train 1: batch statistics (biased variance) through fixed-order two-stage reductions in double; save_mean / save_invstd
+ *            (C floats) receive mean and 1/sqrt(var + eps); running_mean / running_var (NULL together = not tracked) are updated
+ *            on the device with `momentum` (running_var with the unbiased variance); *num_batches_tracked (int64, NULL = none) += 1.
+ *   train 0: running statistics (save_mean / save_invstd are written from them).
+ *   y = lrelu((x - mean) * invstd * gamma + beta); gamma / beta NULL = 1 / 0.  B*HW >= 2 in train mode.
+ *   workspace: rvsr_bn_workspace_bytes(B, C, HW) bytes, forward and backward alike.  Bit-identical from run to run. */
+size_t rvsr_bn_workspace_bytes(int B, int C, int HW);
+int rvsr_bn_lrelu_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          long long* num_batches_tracked, float* y, float* save_mean, float* save_invstd, int B, int C, int HW,
+                          int train, float momentum, float eps, float slope, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the above: gz = gy * (y > 0 ? 1 : slope) from the saved OUTPUT y, xhat = (x - save_mean) * save_invstd;
+ *   ggamma = sum gz * xhat, gbeta = sum gz (per channel, fixed order, double; NULL = skip);
+ *   gx (NULL = skip) = gamma * invstd * (gz - mean(gz) - xhat * mean(gz * xhat)) in train mode, gamma * invstd * gz in eval mode. */
+int rvsr_bn_lrelu_backward(const float* gy, const float* y, const float* x, const float* gamma, const float* save_mean,
+                           const float* save_invstd, float* gx, float* ggamma, float* gbeta, int B, int C, int HW, int train,
+                           float slope, void* workspace, size_t workspace_bytes, void* stream);
+
+/* GAN criterion (GANLoss 'gan' / 'ragan' = BCEWithLogitsLoss, mean): out[0] = scale * sum_i bce(a_i - shift, target),
+ *   shift = mean(b) (b != NULL, nb elements: the relativistic form) or 0; bce(z, t) = max(z, 0) - z t + log1p(exp(-|z|)).
+ *   saved (2 device floats): {shift, sum_i (sigmoid(a_i - shift) - target)} for the backward.  One workgroup, fixed order, double.
+ * Backward: ga_i = g * scale * (sigmoid(a_i - shift) - target); gb_j (gb may be NULL) = -g * scale * saved[1] / nb; g = gscalar[0]
+ *   (device pointer: no host sync). */
+int rvsr_gan_loss_forward(const float* a, size_t na, const float* b, size_t nb, float target, double scale, float* out, float* saved,
+                          void* stream);
+int rvsr_gan_loss_backward(const float* a, size_t na, size_t nb, const float* saved, const float* gscalar, float target, float scale,
+                           float* ga, float* gb, void* stream);
 
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);

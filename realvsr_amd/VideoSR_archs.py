@@ -15,3 +15,17 @@ def define_G(opt):
         return TDAN_arch.TDAN(nf=opt_net['nf'], channel=opt_net['nc'], nframes=opt_net['nframes'], nb_f=opt_net['nb_f'],
                               nb_b=opt_net['nb_b'], groups=opt_net['groups'], scale=opt['scale'])
     raise NotImplementedError('Generator model [{:s}] not recognized'.format(which_model))
+
+
+def define_D(opt):
+    """define_D (codes/models/VideoSR_archs.py:64-105) for the patch discriminators; every other branch is refused."""
+    import torch.nn as nn
+    from .archs import discriminator_arch
+    opt_net = opt['network_D']
+    which_model = opt_net['which_model_D']
+    if which_model == 'PatchDiscriminator':
+        return discriminator_arch.PatchDiscriminator(input_nc=opt_net['in_nc'], ndf=opt_net['nf'], norm_layer=nn.BatchNorm2d)
+    if which_model == 'MultiscaleDiscriminator_v4':
+        return discriminator_arch.MultiscaleDiscriminator_v4(input_nc=opt_net['in_nc'], ndf=opt_net['nf'], num_D=opt_net['num_D'],
+                                                             norm_layer=nn.BatchNorm2d, gan_type=opt_net['gan_type'])
+    raise NotImplementedError('Discriminator model [{:s}] is not built'.format(which_model))

@@ -13,7 +13,8 @@ MI355X wiring instead of DataParallel / DistributedDataParallel + torch.optim.Ad
   * with ``opt['dist']`` every rank (one process per GPU) starts from rank 0's parameters and the gradient buffer is
     all-reduced in buckets over RCCL while backward is still running (dist.BucketedGradAllReduce);
   * augmentation runs as one kernel on the device-resident clip pair (augment.apply_augment).
-Out of scope: LR schedulers, logging, checkpoint cadence, the VGG feature loss and the GAN models.
+Out of scope: LR schedulers, logging, checkpoint cadence, the VGG feature loss.
+``VideoSRGANModel`` below is the GAN stage (VideoSRGAN_AllPair_model_YCbCr_Split.py) on the same machinery.
 """
 import os
 from collections import OrderedDict
@@ -187,11 +188,209 @@ class VideoSRModel:
         torch.save(OrderedDict((k, v.cpu()) for k, v in network.state_dict().items()), save_path)
 
 
+def _gan_pixel_criterion(name, channels):
+    """The pixel-criterion table of the GAN model's constructor (VideoSRGAN_AllPair_model_YCbCr_Split.py:50-115)."""
+    if name == 'ssim':
+        return L.SSIM(channels=channels)
+    if name == 'gw':
+        return L.GWLoss(w=4, reduction='mean')
+    if name in ('l1', 'l2', 'cb', 'hb'):
+        return _criterion(name, 3, 'y')
+    raise NotImplementedError('Loss type [{:s}] is not recognized.'.format(str(name)))
+
+
+class VideoSRGANModel:
+    """``VideoSRGANModel`` of codes/models/VideoSRGAN_AllPair_model_YCbCr_Split.py (:23-183 constructor, :185-191 feed_data, :193-317
+    optimize_parameters): G = the generator of define_G, D = define_D's patch discriminator on the two high-frequency Laplacian bands
+    of Y; pixel terms on the pyramid (SSIM / Charbonnier on the bands, GWLoss on CbCr) + the ('ra')GAN term, then the D step (two
+    backward passes: real, fake).  Both optimizers are FlatAdam; every operator is a HIP kernel (discriminator_arch, loss.GANLoss).
+    The reference's call order of D -- hence the BatchNorm running statistics -- is kept: 5 forwards per RaGAN step, 3 per vanilla step,
+    2 of them skipped on steps without a G update.
+    Out of scope (NotImplementedError): the CPU path, opt['dist'], the VGG feature loss, 'lsgan' / 'wgan-gp', LR schedulers."""
+
+    def __init__(self, opt):
+        self.opt = opt
+        if opt.get('gpu_ids', 0) is None or not torch.cuda.is_available():
+            raise NotImplementedError('realvsr_amd runs on MI355X only: there is no CPU path (gpu_ids=None)')
+        if opt.get('dist'):
+            raise NotImplementedError('VideoSRGANModel: distributed training (two backward passes over two reducers) is not built')
+        self.is_train = opt['is_train']
+        train_opt = opt.get('train') or {}
+        if self.is_train:
+            if (train_opt.get('feature_weight') or 0) > 0:
+                raise NotImplementedError('VideoSRGANModel: the VGG feature loss (feature_weight > 0) is not built')
+            gan_type = train_opt['gan_type']
+            if gan_type not in ('gan', 'ragan'):
+                raise NotImplementedError('VideoSRGANModel: gan_type %r is not built (gan | ragan)' % (gan_type,))
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.schedulers, self.optimizers = [], []
+        self.rank = -1
+
+        self.netG = networks.define_G(opt).to(self.device)
+        self.netD = None
+        if self.is_train:
+            self.netD = networks.define_D(opt).to(self.device)
+            self.netG.train()
+            self.netD.train()
+        self.load()
+        if not self.is_train:
+            return
+
+        def crit(key, channels):
+            if (train_opt.get('pixel_weight_' + key) or 0) > 0:
+                return _gan_pixel_criterion(train_opt['pixel_criterion_' + key], channels), train_opt['pixel_weight_' + key]
+            return None, 0
+        self.cri_pix_s, self.l_pix_w_s = crit('s', 1)
+        self.cri_pix_d, self.l_pix_w_d = crit('d', 1)
+        self.cri_pix_c, self.l_pix_w_c = crit('c', 2)
+        self.cri_gan = L.GANLoss(train_opt['gan_type'], 1.0, 0.0)
+        self.l_gan_w = train_opt['gan_weight']
+        self.D_update_ratio = train_opt.get('D_update_ratio') or 1
+        self.D_init_iters = train_opt.get('D_init_iters') or 0
+
+        self.optimizer_G = FlatAdam([v for v in self.netG.parameters() if v.requires_grad], lr=train_opt['lr_G'],
+                                    weight_decay=train_opt.get('weight_decay_G') or 0, betas=(train_opt['beta1_G'], train_opt['beta2_G']))
+        self.optimizers.append(self.optimizer_G)
+        self.optimizer_D = FlatAdam(list(self.netD.parameters()), lr=train_opt['lr_D'], weight_decay=train_opt.get('weight_decay_D') or 0,
+                                    betas=(train_opt['beta1_D'], train_opt['beta2_D']))
+        self.optimizers.append(self.optimizer_D)
+        self.log_dict = OrderedDict()
+
+    # ------------------------------------------------------------------ data
+    def feed_data(self, data, need_GT=True):
+        self.var_L = data['LQs'].to(self.device)
+        if need_GT:
+            self.var_H = data['GT'].to(self.device)
+            self.var_ref = (data['ref'] if 'ref' in data else data['GT']).to(self.device)
+
+    # ------------------------------------------------------------------ one optimisation step
+    def _set_requires_grad_D(self, flag):
+        for p in self.netD.parameters():
+            p.requires_grad = flag
+
+    def optimize_parameters(self, step, log=True):
+        """``log=False`` skips the .item() host syncs of the reference's log_dict (the device scalars stay in ``self.loss_terms``)."""
+        from . import util
+        # G
+        self._set_requires_grad_D(False)
+        self.optimizer_G.zero_grad()
+        aug = self.opt.get('augment')
+        if aug:
+            self.var_H, self.var_L = augments.apply_augment(self.var_H, self.var_L, aug['augs'], aug['probs'], aug['alphas'], aug['mix_p'])
+        self.fake_H = self.netG(self.var_L)
+        c = self.var_L.size(1) // 2
+        gt = self.var_H[:, c] if self.var_H.dim() == 5 else self.var_H
+        ref = self.var_ref[:, c] if self.var_ref.dim() == 5 else self.var_ref
+        fake_y, fake_c = self.fake_H[:, 0:1], self.fake_H[:, 1:3]
+        real_y, real_c = gt[:, 0:1].contiguous(), gt[:, 1:3].contiguous()
+        fake_pyr = util.laplacian_pyramid(img=fake_y, max_levels=3)
+        real_pyr = util.laplacian_pyramid(img=real_y, max_levels=3)
+        ref_pyr = util.laplacian_pyramid(img=ref[:, 0:1].contiguous(), max_levels=3)
+        ragan = self.cri_gan.gan_type == 'ragan'
+        terms = OrderedDict()
+        if step % self.D_update_ratio == 0 and step > self.D_init_iters:
+            total = 0
+            if self.cri_pix_s is not None:
+                terms['l_g_pix_s'] = self.l_pix_w_s * self.cri_pix_s(fake_pyr[-1], real_pyr[-1])
+                total = total + terms['l_g_pix_s']
+            if self.cri_pix_d is not None:
+                terms['l_g_pix_d'] = self.l_pix_w_d * self.cri_pix_d(fake_pyr[0], real_pyr[0]) + \
+                    self.l_pix_w_d * self.cri_pix_d(fake_pyr[1], real_pyr[1])
+                total = total + terms['l_g_pix_d']
+            if self.cri_pix_c is not None:
+                terms['l_g_pix_c'] = self.l_pix_w_c * self.cri_pix_c(fake_c, real_c)
+                total = total + terms['l_g_pix_c']
+            l_g_gan = 0
+            if ragan:
+                with torch.no_grad():   # (its outputs are detached in the reference: same values, same BN statistics, no graph)
+                    pred_d_real = self.netD(ref_pyr[:-1])
+                pred_g_fake = self.netD(fake_pyr[:-1])
+                for i in range(len(pred_d_real)):
+                    l_g_gan = l_g_gan + self.l_gan_w * (self.cri_gan(pred_d_real[i], False, other=pred_g_fake[i]) +
+                                                        self.cri_gan(pred_g_fake[i], True, other=pred_d_real[i])) / 2
+            else:
+                pred_g_fake = self.netD(fake_pyr[:-1])
+                for i in range(len(pred_g_fake)):
+                    l_g_gan = l_g_gan + self.l_gan_w * self.cri_gan(pred_g_fake[i], True)
+            terms['l_g_gan'] = l_g_gan
+            total = total + l_g_gan
+            terms['l_g_total'] = total
+            total.backward()
+            self.optimizer_G.step()
+
+        # D
+        self._set_requires_grad_D(True)
+        self.optimizer_D.zero_grad()
+        fake_in = [x.detach() for x in fake_pyr[:-1]]
+        real_in = ref_pyr[:-1]
+        l_d_real, l_d_fake = 0, 0
+        if ragan:
+            with torch.no_grad():
+                pred_d_fake = self.netD(fake_in)
+            pred_d_real = self.netD(real_in)
+            for i in range(len(pred_d_fake)):
+                l_d_real = l_d_real + self.cri_gan(pred_d_real[i], True, other=pred_d_fake[i]) * 0.5
+            l_d_real.backward()
+            pred_d_fake = self.netD(fake_in)
+            for i in range(len(pred_d_fake)):
+                l_d_fake = l_d_fake + self.cri_gan(pred_d_fake[i], False, other=pred_d_real[i].detach()) * 0.5
+            l_d_fake.backward()
+        else:
+            pred_d_real = self.netD(real_in)
+            for i in range(len(pred_d_real)):
+                l_d_real = l_d_real + self.cri_gan(pred_d_real[i], True)
+            l_d_real.backward()
+            pred_d_fake = self.netD(fake_in)
+            for i in range(len(pred_d_fake)):
+                l_d_fake = l_d_fake + self.cri_gan(pred_d_fake[i], False)
+            l_d_fake.backward()
+        self.optimizer_D.step()
+        terms['l_d_real'] = l_d_real.detach()
+        terms['l_d_fake'] = l_d_fake.detach()
+        self.loss_terms = terms
+        if log:
+            for k, v in terms.items():
+                self.log_dict[k] = v.item()
+
+    def test(self):
+        self.netG.eval()
+        with torch.no_grad():
+            self.fake_H = self.netG(self.var_L)
+        self.netG.train()
+
+    # ------------------------------------------------------------------ bookkeeping
+    def get_current_log(self):
+        return self.log_dict
+
+    def get_current_visuals(self, need_GT=True):
+        out = OrderedDict()
+        out['LQs'] = self.var_L.detach()[0].float().cpu()
+        out['HQ'] = self.fake_H.detach()[0].float().cpu()
+        if need_GT:
+            out['GT'] = self.var_H.detach()[0].float().cpu()
+        return out
+
+    def get_current_learning_rate(self):
+        return [g['lr'] for g in self.optimizers[0].param_groups]
+
+    def load(self):
+        path = self.opt.get('path') or {}
+        strict = path.get('strict_load', True)
+        if path.get('pretrain_model_G') is not None:
+            VideoSRModel.load_network(self, path['pretrain_model_G'], self.netG, strict)
+        if self.is_train and path.get('pretrain_model_D') is not None:
+            VideoSRModel.load_network(self, path['pretrain_model_D'], self.netD, strict)
+
+    load_network = VideoSRModel.load_network
+    save_network = VideoSRModel.save_network
+
+
 def create_model(opt):
     model = opt['model']
     if model == 'VideoSR_AllPair_YCbCr_Split':
         return VideoSRModel(opt, split=True)
     if model == 'VideoSR_AllPair_YCbCr_Combine':
         return VideoSRModel(opt, split=False)
-    # VideoSRGAN_AllPair_YCbCr_Split (discriminators, GAN losses) is outside the hot path
+    if model == 'VideoSRGAN_AllPair_YCbCr_Split':
+        return VideoSRGANModel(opt)
     raise NotImplementedError('Model [{:s}] not recognized.'.format(str(model)))

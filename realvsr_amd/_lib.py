@@ -77,6 +77,11 @@ SIGNATURES = {
     'rvsr_bcast_add_act': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_float, c_fp]),
     'rvsr_bcast_reduce_act': (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_float, c_fp]),
     'rvsr_augment_clips': (c_int, [c_fp] * 5 + [c_size] + [c_int] * 10 + [c_float, c_fp]),
+    'rvsr_bn_workspace_bytes': (c_size, [c_int] * 3),
+    'rvsr_bn_lrelu_forward': (c_int, [c_fp] * 9 + [c_int] * 4 + [c_float] * 3 + [c_fp, c_size, c_fp]),
+    'rvsr_bn_lrelu_backward': (c_int, [c_fp] * 9 + [c_int] * 4 + [c_float, c_fp, c_size, c_fp]),
+    'rvsr_gan_loss_forward': (c_int, [c_fp, c_size, c_fp, c_size, c_float, c_double, c_fp, c_fp, c_fp]),
+    'rvsr_gan_loss_backward': (c_int, [c_fp, c_size, c_size, c_fp, c_fp, c_float, c_float, c_fp, c_fp, c_fp]),
     'rvsr_debug_mfma_rate': (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
 }
 

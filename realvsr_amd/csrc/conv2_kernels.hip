@@ -990,8 +990,8 @@ static inline bool f16fp8_ok(int ksize, int stride, int mt, int w_mode) { return
 static void fwd2_geom(int ksize, int Co, int Ctot, int& mt, int& ccg, int& nchunks, int& nmb) {
     // never more than 2 M tiles per workgroup: the MT = 4 instantiation keeps 128 accumulator registers live and
     // spills (130-190 VGPRs to scratch); two 64-row m-blocks re-stage the input tile but run spill-free
-    mt = Co <= 32 ? 1 : 2;
-    ccg = ksize == 3 ? 1 : 2;
+    mt = (Co <= 32 || ksize == 5) ? 1 : 2;   // (5x5: 32-row m-blocks keep the 25-tap weight slice at 78 / 133 KB of LDS, stride 1 / 2)
+    ccg = ksize == 1 ? 2 : 1;
     nchunks = (Ctot + 16 * ccg - 1) / (16 * ccg);
     nmb = (Co + mt * 32 - 1) / (mt * 32);
 }
@@ -1098,7 +1098,8 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspac
     fwd2_geom(ksize, p.Co, Ctot, mt, ccg, nchunks, nmb);
     const size_t need = rvsr_conv_fwd2_workspace_bytes(ksize, p.Co, Ctot);
     if (!workspace || workspace_bytes < need) FAIL(RVSR_ERR_WORKSPACE, "conv2d: workspace %zu B < %zu B", workspace_bytes, need);
-    if ((ksize == 1 || stride == 2) && p.in.a.mode == 0) {
+    if (ksize == 5 && p.in.a.mode == 1) return RVSR_ERR_UNSUPPORTED;   // (conv_fwd2 stages plain and pixel-unshuffle views only)
+    if ((ksize != 3 || stride == 2) && p.in.a.mode == 0) {
         // conv_fwd2_kernel stages a plain view through raw buffer loads: 32-bit byte offsets inside one batch element (< 2 GB),
         // and a concat boundary on a chunk boundary; anything else goes back to the exact-f32 kernels of conv_kernels.hip
         const size_t span = sizeof(float) * (size_t)p.in.a.Hs * p.in.a.Ws * (size_t)(p.in.a.C > p.in.b.C ? p.in.a.C : p.in.b.C);
@@ -1124,6 +1125,7 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspac
     } while (0)
     if (ksize == 3 && stride == 1) return mt == 1 ? launch_fwd5<1>(p, st) : launch_fwd5<2>(p, st);
     if (ksize == 3 && stride == 2) DISPATCH2(3, 2, 1);
+    if (ksize == 5) return stride == 1 ? launch_fwd2<5, 1, 1, 1>(p, st) : launch_fwd2<5, 2, 1, 1>(p, st);
     DISPATCH2(1, 1, 2);
 #undef DISPATCH2
 }
@@ -1134,6 +1136,7 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspac
 extern "C" size_t rvsr_conv2d_pack_weights(const float* weight, int C_in, int Co, int ksize, int w_mode, void* out, size_t out_bytes,
                                            long long* desc, void* stream) {
     int mt, ccg, nchunks, nmb;
+    if (ksize != 1 && ksize != 3 && ksize != 5) return 0;
     fwd2_geom(ksize, Co, C_in, mt, ccg, nchunks, nmb);
     const size_t need = rvsr_conv_fwd2_workspace_bytes(ksize, Co, C_in);
     if (!weight || !out || out_bytes < need) return 0;
@@ -1754,5 +1757,122 @@ int rvsr_launch_conv_wgrad_s2(const ConvWgradParams& p, int gy, int gz, hipStrea
     hipLaunchKernelGGL(k, dim3(p.P, gy, gz), dim3(256), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad_s2 launch: %s", hipGetErrorString(e));
+    return RVSR_OK;
+}
+
+// ==========================================================================================
+// Weight gradient of a 5x5 convolution (stride 1 or 2, pad 2; the patch discriminator) on the bf16 matrix cores:
+//   gW[o][c][tap] = sum_px G[o][px] * X[c][px shifted by tap],   K = pixels.
+// One workgroup = 4 waves = a 32(o) x 32(c) block of gW for all 25 taps over a persistent slice of 4 x 32-pixel tiles (K split,
+// deterministic partials reduced by rvsr_reduce_partials_kernel, the layout of conv_wgrad_kernel).  G and X tiles are staged in LDS
+// as f32 (odd row strides: conflict-free lane reads); each MFMA operand (8 consecutive pixels per lane) is read from there and split
+// into bf16 hi / lo in registers.  Wave w owns the taps w, w + 4, ..., i.e. one 32 x 32 accumulator per tap (7 at most).
+// NT: terms of the product, as conv_wgrad2 (3 = hi*hi + hi*lo + lo*hi; 2 = without the lo part of the output gradient; 1 = hi*hi).
+template <int STRIDE, int NT>
+__global__ __launch_bounds__(256, 1) void conv_wgrad5_kernel(const ConvWgradParams p) {
+    constexpr int KS = 5, T = 25, PAD = 2, TH = 4, TW = 32, NPX = TH * TW, TPW = 7;
+    constexpr int IH = (TH - 1) * STRIDE + KS, IW = (TW - 1) * STRIDE + KS;
+    constexpr int CS = (IH * IW) | 1, GS = NPX + 1;
+    extern __shared__ __attribute__((aligned(16))) float smem5[];
+    float* gT = smem5;             // [32 o][GS]
+    float* xs = smem5 + 32 * GS;   // [32 c][CS]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 31, hi = lane >> 5;
+    const int mb = blockIdx.y, c0 = blockIdx.z * 32;
+    const int Ctot = p.x.a.C + p.x.b.C;
+    int xoff[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        const int tap = wave + 4 * i;
+        xoff[i] = tap < T ? lo * CS + (tap / KS) * IW + (tap % KS) : 0;
+    }
+    f32x16 acc[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        acc[i] = zero16();
+        asm volatile("" : "+v"(acc[i]));   // (no SrcC = 0 form for the first product: see mfma_bf16_first)
+    }
+    float bsum = 0.f;
+    const int ntiles = p.B * p.nty * p.ntx;
+    for (int tile = blockIdx.x; tile < ntiles; tile += p.P) {
+        const int b = tile / (p.nty * p.ntx);
+        const int trem = tile - b * (p.nty * p.ntx);
+        const int ty = trem / p.ntx, tx = trem - ty * p.ntx;
+        const int y0 = ty * TH, x0 = tx * TW;
+#pragma unroll 4
+        for (int e = tid; e < 32 * NPX; e += 256) {
+            const int ol = e / NPX, px = e - ol * NPX;
+            gT[ol * GS + px] = tview_get(p.g, b, mb * 32 + ol, y0 + (px >> 5), x0 + (px & 31));   // (0 beyond Co / the frame)
+        }
+#pragma unroll 4
+        for (int e = tid; e < 32 * IH * IW; e += 256) {
+            const int cc = e / (IH * IW), rem = e - cc * (IH * IW);
+            const int r = rem / IW, s = rem - r * IW;
+            xs[cc * CS + r * IW + s] = tcat_get(p.x, b, c0 + cc, y0 * STRIDE - PAD + r, x0 * STRIDE - PAD + s);   // (0 beyond Ctot)
+        }
+        __syncthreads();
+        if (p.bpart != nullptr && blockIdx.z == 0 && tid < 32) {
+            float s = 0.f;
+            for (int px = 0; px < NPX; ++px) s += gT[tid * GS + px];
+            bsum += s;
+        }
+#pragma unroll 1
+        for (int ks = 0; ks < NPX / 16; ++ks) {
+            const int row = ks >> 1, col0 = (ks & 1) * 16 + 8 * hi;
+            float av[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) av[q] = gT[lo * GS + row * 32 + col0 + q];
+            bf16x8 ah, al;
+            split8(av, ah, al);
+            const int poff = row * STRIDE * IW + col0 * STRIDE;
+#pragma unroll
+            for (int i = 0; i < TPW; ++i) {
+                if (wave + 4 * i >= T) continue;   // (uniform per wave)
+                float bv[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) bv[q] = xs[xoff[i] + poff + q * STRIDE];
+                bf16x8 bh, bl;
+                split8(bv, bh, bl);
+                acc[i] = mfma_bf16(ah, bh, acc[i]);
+                if (NT >= 2) acc[i] = mfma_bf16(ah, bl, acc[i]);
+                if (NT >= 3) acc[i] = mfma_bf16(al, bh, acc[i]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        const int tap = wave + 4 * i, c = c0 + lo;
+        if (tap >= T || c >= Ctot) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = mb * 32 + drow(r, hi);
+            if (o < p.Co) p.part[(((size_t)blockIdx.x * p.Co + o) * Ctot + c) * T + tap] = acc[i][r];
+        }
+    }
+    if (p.bpart != nullptr && blockIdx.z == 0 && tid < 32) {
+        const int o = mb * 32 + tid;
+        if (o < p.Co) p.bpart[(size_t)blockIdx.x * p.Co + o] = bsum;
+    }
+}
+
+int rvsr_conv_wgrad5_P(int B, int Hout, int Wout, int Co, int Ctot) {
+    const long ntiles = (long)B * ((Hout + 3) / 4) * ((Wout + 31) / 32);
+    long P = 256 / ((long)((Co + 31) / 32) * ((Ctot + 31) / 32));
+    if (P < 1) P = 1;
+    if (P > ntiles) P = ntiles;
+    return (int)P;
+}
+
+int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, hipStream_t st) {
+    const int Ctot = p.x.a.C + p.x.b.C;
+    const int IH = 3 * stride + 5, IW = 31 * stride + 5;
+    const size_t lds = sizeof(float) * (32 * (4 * 32 + 1) + 32 * ((IH * IW) | 1));
+    const int nt = rvsr_gemm_terms();
+    auto k = stride == 1 ? (nt == 1 ? conv_wgrad5_kernel<1, 1> : nt == 2 ? conv_wgrad5_kernel<1, 2> : conv_wgrad5_kernel<1, 3>)
+                         : (nt == 1 ? conv_wgrad5_kernel<2, 1> : nt == 2 ? conv_wgrad5_kernel<2, 2> : conv_wgrad5_kernel<2, 3>);
+    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad5: cannot reserve %zu B of LDS", lds);
+    hipLaunchKernelGGL(k, dim3(p.P, (p.Co + 31) / 32, (Ctot + 31) / 32), dim3(256), lds, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad5 launch: %s", hipGetErrorString(e));
     return RVSR_OK;
 }

@@ -91,6 +91,9 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspac
 int rvsr_launch_conv_wgrad2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad1x1(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad_s2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
+// 5x5 (stride 1 / 2) weight gradient on the bf16 matrix cores: one partial per workgroup of its own grid (P from rvsr_conv_wgrad5_P)
+int rvsr_conv_wgrad5_P(int B, int Hout, int Wout, int Co, int Ctot);
+int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, hipStream_t st);
 // conv_thin_kernels.hip: 3x3 / stride-1 layers with <= 4 output channels on the vector ALU (exact f32)
 int rvsr_conv_wgrad_thin_P(int B, int Hout, int Wout);
 int rvsr_launch_conv_wgrad_thin(const ConvWgradParams& p, hipStream_t st);

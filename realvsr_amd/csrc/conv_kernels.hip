@@ -310,8 +310,8 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     if (!x1 || !weight || !out1 || B <= 0 || C1 <= 0 || Co1 <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d: null/empty argument");
     if ((x2 == nullptr) != (C2 == 0) || (out2 == nullptr) != (Co2 == 0))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: second input/output pointer and channel count disagree");
-    if (ksize != 1 && ksize != 3) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: kernel size %d (1 or 3 supported)", ksize);
-    if (stride != 1 && !(stride == 2 && ksize == 3)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: stride %d", stride);
+    if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 or 5 supported)", ksize);
+    if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: stride %d", stride);
     if (in_mode != 0 && (x2 != nullptr || stride != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: view mode with concat/stride");
     if (xact && x2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: act' fusion with concat input");
     if ((residual || pixel_shuffle) && out2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual/pixel-shuffle with split output");
@@ -351,6 +351,8 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
         return rvsr_launch_conv_fwd2(p, ksize, stride, workspace, workspace_bytes, st);
     }
     if (rvsr_conv_fwd_thin_ok(p, ksize, stride)) return rvsr_launch_conv_fwd_thin(p, st);   // <= 4 output channels: vector ALU, exact f32
+    // 5x5 (the patch discriminator, archs/discriminator_arch.py): conv_fwd2 at KS = 5 except through the zero-insert view of a stride-2
+    // data gradient (in_mode 1), which only the 3x3 kernels stage: that one takes the exact-f32 kernels below
     if (rvsr_gemm_mode_now() != 1 && (in_mode != 1 || ksize == 3) && (x2 == nullptr || C1 % 8 == 0)) {
         const int rc2 = rvsr_launch_conv_fwd2(p, ksize, stride, workspace, workspace_bytes, st);
         if (rc2 != RVSR_ERR_UNSUPPORTED) return rc2;   // (sizes beyond the buffer-addressed kernels: exact-f32 kernels below)
@@ -364,6 +366,8 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     } while (0)
     if (ksize == 3 && stride == 1) DISPATCH(3, 1, 16, 8);
     if (ksize == 3 && stride == 2) DISPATCH(3, 2, 8, 4);
+    if (ksize == 5 && stride == 1) DISPATCH(5, 1, 8, 4);     // LDS: 66 / 58 KB (2 workgroups per CU)
+    if (ksize == 5) DISPATCH(5, 2, 4, 4);                    // 34 / 46 / 72 KB
     DISPATCH(1, 1, 32, 32);
 #undef DISPATCH
 }
@@ -393,7 +397,8 @@ static int wgrad_s2_P(int B, int Hout, int Wout, int gy, int gz64) {
     return P;
 }
 static void wgrad_geom(int ksize, int stride, int Co, int Ctot, int& ccw, int& gy, int& gz) {
-    ccw = (ksize == 3 && stride == 2) ? 32 : 64;
+    // 5x5: 16 input channels per workgroup = 400 GEMM columns, 7 accumulator tiles per wave (64 would need 25)
+    ccw = ksize == 5 ? 16 : ((ksize == 3 && stride == 2) ? 32 : 64);
     gy = (Co + 63) / 64;
     gz = (Ctot + ccw - 1) / ccw;
 }
@@ -407,6 +412,10 @@ extern "C" size_t rvsr_conv2d_wgrad_workspace_bytes(int C1, int C2, int Co, int 
     if (ksize == 3 && stride == 2) {  // the bf16x3 stride-2 kernel slices the pixels differently
         const size_t P2 = wgrad_s2_P(B, Hout, Wout, gy, (C1 + C2 + 63) / 64);
         if (P2 > P) P = P2;
+    }
+    if (ksize == 5) {   // so does the bf16x3 5x5 kernel
+        const size_t P5 = rvsr_conv_wgrad5_P(B, Hout, Wout, Co, C1 + C2);
+        if (P5 > P) P = P5;
     }
     if (ksize == 3 && stride == 1 && Co <= 4) {  // the thin-layer kernel keeps one partial per workgroup of its own grid
         const size_t P3 = rvsr_conv_wgrad_thin_P(B, Hout, Wout);
@@ -434,8 +443,8 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
                                            size_t workspace_bytes, void* stream) {
     if (!x1 || !gout || !grad_weight || B <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: null/empty argument");
     if ((x2 == nullptr) != (C2 == 0)) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: x2/C2 disagree");
-    if (ksize != 1 && ksize != 3) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: kernel size %d", ksize);
-    if (stride != 1 && !(stride == 2 && ksize == 3)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: stride %d", stride);
+    if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: kernel size %d", ksize);
+    if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: stride %d", stride);
     if (g_mode != 0 && g_mode != 2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: gradient view mode %d", g_mode);
     const size_t need = rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, ksize, stride, Hout, Wout);
     if (!workspace || workspace_bytes < need)
@@ -484,6 +493,12 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
     if (rvsr_gemm_mode_now() != 1 && ksize == 3 && stride == 1 && (Wout % 4) == 0 && aligned16 && img_max < ((size_t)1 << 31) &&
         (C2 == 0 || C1 % 64 == 0))
         rc = rvsr_launch_conv_wgrad2(p, gy, gz, st);
+    else if (ksize == 5 && rvsr_gemm_mode_now() != 1) {   // bf16 matrix cores (the mode's terms), deterministic partials like the others
+        p.P = rvsr_conv_wgrad5_P(B, Hout, Wout, Co, Ctot);
+        p.bpart = grad_bias ? p.part + (size_t)p.P * nw : nullptr;
+        rc = rvsr_launch_conv_wgrad5(p, stride, st);
+    } else if (ksize == 5)   // exact-f32 mode
+        rc = stride == 1 ? launch_wgrad<5, 1, 16>(p, gy, gz, st) : launch_wgrad<5, 2, 16>(p, gy, gz, st);
     else if (rvsr_gemm_mode_now() != 1 && ksize == 1 && g_mode == 0 && ((Hout * Wout) % 8) == 0 && aligned16)
         rc = rvsr_launch_conv_wgrad1x1(p, gy, gz, st);
     else if (ksize == 3 && stride == 1)

@@ -290,6 +290,8 @@ def _conv_fwd(L, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias
     if (_lib.fmt_f16fp8() and k == 3 and stride == 1 and w_mode == 0 and Co1 + Co2 > 32 and not xact and in_mode == 0 and Ws % 4 == 0
             and (C2 == 0 or C1 % 16 == 0) and ((getattr(x1, 'value', None) or 0) | (getattr(x2, 'value', None) or 0)) % 16 == 0):
         w_mode |= 4     # 'f16fp8' mode: this forward conv in the f16 + fp8 product format (weight image and kernel; _lib.set_gemm_mode)
+    if k == 5 and in_mode == 1:
+        wparam = None   # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused)
     buf = packed_weights.get(wparam, 'conv', C1 + C2, Co1 + Co2, k, w_mode, nbytes) if wparam is not None else None
     if buf is not None:
         ws, w_mode = buf, w_mode | 2
@@ -1520,6 +1522,101 @@ def augment_clips(im1, im2, perm=(0, 1, 2), box_mode=0, box=(0, 0, 0, 0), v=1.0,
                                                  int(box[1]), int(box[2]), int(box[3]), float(v), _stream()),
                    'augment_clips')
     return out1, out2
+
+
+# ------------------------------------------------------------------------------------------ GAN discriminator
+class _BatchNormLReLU(Function):
+    """lrelu(batch_norm(x), slope) as one operator (the BN -> LeakyReLU(0.2) pairs of discriminator_arch.PatchDiscriminator).
+    Train mode: batch statistics, running statistics and num_batches_tracked updated on the device; eval: running statistics."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, train, momentum, eps, slope):
+        _need_cuda(x, weight, bias, running_mean, running_var)
+        if num_batches_tracked is not None and (not num_batches_tracked.is_cuda or num_batches_tracked.dtype != torch.int64):
+            raise TypeError('bn_lrelu: num_batches_tracked must be an int64 device tensor')
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        y = torch.empty_like(x)
+        mean, invstd = x.new_empty(C), x.new_empty(C)
+        L = _lib.lib()
+        ws = _workspace(L.rvsr_bn_workspace_bytes(B, C, H * W), x.device)
+        _lib.check(L.rvsr_bn_lrelu_forward(_p(x), _p(weight), _p(bias), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(y),
+                                           _p(mean), _p(invstd), B, C, H * W, int(train), momentum, eps, slope, _p(ws), ws.numel(),
+                                           _stream()), 'bn_lrelu_forward')
+        ctx.cfg = (bool(train), slope)
+        ctx.weight_p, ctx.bias_p = weight, bias
+        ctx.save_for_backward(x, y, weight, mean, invstd)
+        ctx.mark_non_differentiable(mean, invstd)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, y, weight, mean, invstd = ctx.saved_tensors
+        train, slope = ctx.cfg
+        B, C, H, W = x.shape
+        gy = gy.contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw = _pgrad(ctx.weight_p) if ctx.needs_input_grad[1] else None
+        gb = _pgrad(ctx.bias_p) if ctx.needs_input_grad[2] else None
+        L = _lib.lib()
+        ws = _workspace(L.rvsr_bn_workspace_bytes(B, C, H * W), x.device)
+        _lib.check(L.rvsr_bn_lrelu_backward(_p(gy), _p(y), _p(x), _p(weight), _p(mean), _p(invstd), _p(gx), _p(gw), _p(gb), B, C, H * W,
+                                            int(train), slope, _p(ws), ws.numel(), _stream()), 'bn_lrelu_backward')
+        return gx, gw, gb, None, None, None, None, None, None, None
+
+
+def batch_norm_lrelu(x, bn, slope=0.2):
+    """lrelu(bn(x), slope) for an ``nn.BatchNorm2d`` ``bn`` with torch's train / eval semantics (running statistics tracked with
+    ``bn.momentum``; num_batches_tracked += 1 per train-mode call)."""
+    if bn.momentum is None:
+        raise NotImplementedError('bn_lrelu: momentum=None (cumulative moving average) is not supported')
+    use_batch = bn.training or bn.running_mean is None
+    track = bn.training and bn.track_running_stats and bn.running_mean is not None
+    rm = bn.running_mean if (track or not use_batch) else None
+    rv = bn.running_var if (track or not use_batch) else None
+    nbt = bn.num_batches_tracked if track else None
+    return _BatchNormLReLU.apply(x, bn.weight, bn.bias, rm, rv, nbt, use_batch, float(bn.momentum), float(bn.eps), float(slope))
+
+
+class _GANCriterion(Function):
+    """mean(BCEWithLogits(a - shift, target)), shift = mean(b) (relativistic) or 0."""
+
+    @staticmethod
+    def forward(ctx, a, b, target):
+        _need_cuda(a, b)
+        a = a.contiguous()
+        b = _c(b)
+        out = a.new_empty(())
+        saved = a.new_empty(2)
+        scale = 1.0 / a.numel()
+        nb = 0 if b is None else b.numel()
+        _lib.check(_lib.lib().rvsr_gan_loss_forward(_p(a), a.numel(), _p(b), nb, target, scale, _p(out), _p(saved), _stream()),
+                   'gan_loss_forward')
+        ctx.cfg = (target, scale, nb, b.shape if b is not None else None)
+        ctx.save_for_backward(a, saved)
+        ctx.mark_non_differentiable(saved)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, saved = ctx.saved_tensors
+        target, scale, nb, bshape = ctx.cfg
+        g = g.contiguous()
+        ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        gb = a.new_empty(bshape) if (nb and ctx.needs_input_grad[1]) else None
+        if ga is None and gb is None:
+            return None, None, None
+        _lib.check(_lib.lib().rvsr_gan_loss_backward(_p(a), a.numel(), nb, _p(saved), _p(g), target, scale, _p(ga), _p(gb), _stream()),
+                   'gan_loss_backward')
+        return ga, gb, None
+
+
+def gan_criterion(a, target, other=None):
+    """``BCEWithLogitsLoss()(a, full_like(a, target))``; with ``other``: ``(a - mean(other), target)`` -- the relativistic term of
+    RaGAN, the gradient reaching ``other`` through the mean (VideoSRGAN_AllPair_model_YCbCr_Split.py:253-258, 286-296)."""
+    return _GANCriterion.apply(a, other, float(target))
 
 
 # ------------------------------------------------------------------------------------------ device guard

@@ -90,6 +90,24 @@ class GWLoss(nn.Module):
         return RF.gw_loss(x1, x2, self.w, 'mean' if self.reduction == 'mean' else 'sum')
 
 
+class GANLoss(nn.Module):
+    """GAN loss (codes/models/loss.py:102-133) for 'gan' and 'ragan': BCEWithLogitsLoss (mean) against a constant label, one HIP
+    reduction.  ``other`` (an addition for RaGAN) scores ``input - mean(other)`` with the gradient reaching ``other`` through the mean,
+    so the model never composes that difference from torch ops.  'lsgan' / 'wgan-gp' are not built (NotImplementedError)."""
+
+    def __init__(self, gan_type, real_label_val=1.0, fake_label_val=0.0):
+        super(GANLoss, self).__init__()
+        self.gan_type = gan_type.lower()
+        self.real_label_val = real_label_val
+        self.fake_label_val = fake_label_val
+        if self.gan_type not in ('gan', 'ragan'):
+            raise NotImplementedError('GAN type [{:s}] is not built (gan | ragan)'.format(self.gan_type))
+
+    def forward(self, input, target_is_real, other=None):
+        target = self.real_label_val if target_is_real else self.fake_label_val
+        return RF.gan_criterion(input, target, other)
+
+
 class PyramidLoss(nn.Module):
     """Pyramid Loss"""
 
