@@ -247,11 +247,12 @@ int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const 
  *   caller-owned memory of rvsr_conv2d_forward_workspace_bytes(C_in, 0, Co, ksize) /
  *   rvsr_modulated_deform_conv_forward_workspace_bytes(channels, channels_out) bytes and return that size (0 = bad argument);
  *   `desc` (NULL or 10 x long long, host; 20 x long long for rvsr_dcn_pack_weights) receives {weight, out, Co, C_in, taps, MP, CCG,
- *   nchunks, nmb, mode}.  The DCN forward keeps TWO images in that buffer -- the tap-major one of dcn_fwd2 / dcn_fwd3 (mode 0)
- *   and, behind it, the k-step-major one of dcn_fwd4 (mode 2; desc[10..19], all zero where that kernel does not apply: C % 16 != 0).
+ *   nchunks, nmb, mode}.  The DCN forward keeps ONE image in that buffer, the tap-major one of its kernels (mode 0, desc[0..9]);
+ *   rvsr_dcn_pack_weights still WRITES 20 values: desc[10..19] was the descriptor of a second, k-step-major image whose kernel has
+ *   left the library, and is always all zero -- the caller's array must hold 20, only the first 10 mean anything.
  *   rvsr_pack_weights_batched re-packs n images in ONE launch from a DEVICE table of 48-byte records
  *   {const float* w; void* out; int Co, C_in, taps, MP, CCG, nchunks, nmb, mode;} built from those descriptors: the host
- *   (realvsr_amd.functional.PackedWeights) calls it once after the optimizer has updated the parameters in place. */
+ *   (realvsr_amd.caches.PackedWeights) calls it once after the optimizer has updated the parameters in place. */
 size_t rvsr_conv2d_pack_weights(const float* weight, int C_in, int Co, int ksize, int w_mode, void* out, size_t out_bytes,
                                 long long* desc, void* stream);
 int rvsr_pack_weights_batched(const void* descs, int n, void* stream);

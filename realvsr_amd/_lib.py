@@ -7,6 +7,8 @@ import ctypes
 import os
 import subprocess
 
+import torch  # (also loads libamdhip64, which the .so links against)
+
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 SO_PATH = os.environ.get('RVSR_SO', os.path.join(_CSRC, 'librealvsr_hip.so'))  # RVSR_SO: developer override for A/B builds
 _lib = None
@@ -86,6 +88,15 @@ SIGNATURES = {
 }
 
 
+def _p(t):
+    """Device pointer of a tensor (None -> NULL)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def build(verbose=False):
     """Compile every HIP source for gfx950 into csrc/librealvsr_hip.so (hipcc cross-compiles
     without a GPU)."""
@@ -103,7 +114,6 @@ def lib():
             raise RuntimeError(
                 'realvsr_amd: %s is missing -- run `python -c "import __graft_entry__ as g; g.build()"` '
                 '(or `make -C realvsr_amd/csrc`).  There is no CPU / eager fallback.' % SO_PATH)
-        import torch  # noqa: F401  (loads libamdhip64 the .so links against)
         handle = ctypes.CDLL(SO_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the header and the library disagree

@@ -5,27 +5,18 @@ path runs in the HIP kernels (realvsr_amd/csrc).  Each ``Function`` below wraps 
 operator; CPU tensors are refused (NotImplementedError, like the reference's operator:
 codes/models/archs/dcn/deform_conv.py:109-110,124-125).
 """
-import ctypes
 import functools
-
-import os
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import _p, _stream
+from .caches import DcnOffsetStats, PackedWeights, dcn_offset_stats, packed_weights   # noqa: F401  (part of this module's surface)
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 ACT_MASK = 3   # rvsr_conv2d_forward only: out = conv * act'(residual) (include/realvsr_hip.h); internal to the fused backward nodes
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _need_cuda(*ts, any_float=False):
@@ -122,157 +113,7 @@ def _pgrad(p, zero=False):
     return torch.zeros_like(p) if zero else torch.empty_like(p)
 
 
-
-_PACK_VERIFY = False   # debug (set it from a test): on a cache hit, pack the weight again and compare
-
-
-# ------------------------------------------------------------------------------------------ packed weights, once per step
-class PackedWeights:
-    """bf16 hi/lo weight images (what the conv / DCN kernels stage into LDS), packed ONCE per optimizer step.
-
-    A conv block needs its weights re-packed ([m-block][chunk][hi|lo][tap][octet][row][8] bf16) -- once for the forward and once,
-    transposed and flipped, for the data gradient.  The library does that per call into the workspace (~150 launches of a 5 us
-    kernel per training step).  Here the images of parameters that live in optim.FlatBuffers are kept in their own tensors,
-    the first use of an image packs it with one call (rvsr_conv2d_pack_weights / rvsr_dcn_pack_weights), and from then on
-    ``FlatAdam.step`` re-packs ALL registered images with ONE launch (rvsr_pack_weights_batched) right after the update.
-    Validity: an entry is used only while (a) the very same parameter object is alive, (b) its torch version counter is
-    unchanged (load_state_dict, in-place edits under no_grad bump it) and (c) it was packed in the current epoch; everything
-    that writes parameters behind torch's back (the flat Adam kernel, a broadcast into the flat buffer, a raw copy into it) must
-    call ``repack()`` (re-pack now) or ``invalidate()`` (forget).  Foreign weights (not in FlatBuffers) take the per-call path.
-    RVSR_PACK_CACHE=0 turns the cache off."""
-
-    def __init__(self):
-        self.entries = {}          # key -> [packed tensor, weakref(weight), version, epoch, desc (10 ints), weight.data_ptr()]
-        self.slices = {}           # (id(weight), C1) -> [w_a, w_b, weakref(weight), version, epoch, data_ptr]
-        self.epoch = 0
-        self.table = None          # device copy of the descriptor table, rebuilt when entries were added or dropped
-        self.enabled = os.environ.get('RVSR_PACK_CACHE', '1') != '0'
-        self.stats = {'hits': 0, 'packs': 0, 'batched': 0}
-
-    def invalidate(self):
-        self.entries.clear()
-        self.slices.clear()
-        self.table = None
-        self.epoch += 1
-
-    @staticmethod
-    def _version(t):
-        """Version of the parameter a weight tensor stands for: its own, or its parent's for a cached input-channel slice."""
-        parent = getattr(t, '_rvsr_parent', None)
-        if parent is None:
-            return t._version
-        parent = parent()
-        return -1 if parent is None else parent._version
-
-    def split(self, weight, C1):
-        """weight[:, :C1] and weight[:, C1:] as PERSISTENT contiguous tensors (conv_cat_bcast convolves the two halves of a concat
-        conv separately): copied on first sight and after every optimizer step (repack), so that their packed images can be
-        cached like those of whole parameters.  Falls back to fresh copies for weights outside FlatBuffers."""
-        if not self.enabled or getattr(weight, '_rvsr_grad_home', None) is None:
-            return weight[:, :C1].contiguous(), weight[:, C1:].contiguous()
-        import weakref
-        key = (id(weight), C1)
-        e = self.slices.get(key)
-        if e is not None and e[2]() is weight and e[3] == weight._version and e[4] == self.epoch and e[5] == weight.data_ptr():
-            return e[0], e[1]
-        if e is not None and e[2]() is weight and e[0].device == weight.device:
-            w_a, w_b = e[0], e[1]
-            with torch.no_grad():
-                w_a.copy_(weight[:, :C1])
-                w_b.copy_(weight[:, C1:])
-        else:
-            w_a, w_b = weight[:, :C1].detach().contiguous(), weight[:, C1:].detach().contiguous()
-            w_a._rvsr_parent = w_b._rvsr_parent = weakref.ref(weight)
-        self.slices[key] = [w_a, w_b, weakref.ref(weight), weight._version, self.epoch, weight.data_ptr()]
-        return w_a, w_b
-
-    def get(self, weight, kind, C_in, Co, k, w_mode, nbytes):
-        """Packed image tensor for (weight, kind, geometry), or None when the weight is not cacheable."""
-        if not self.enabled or _lib.get_gemm_mode() == 'f32':
-            return None
-        if getattr(weight, '_rvsr_grad_home', None) is None and getattr(weight, '_rvsr_parent', None) is None:
-            return None
-        key = (id(weight), kind, C_in, Co, k, w_mode)
-        e = self.entries.get(key)
-        if e is not None and e[1]() is weight and e[2] == self._version(weight) and e[3] == self.epoch and e[5] == weight.data_ptr():
-            self.stats['hits'] += 1
-            if _PACK_VERIFY:
-                self._verify(e, weight, kind, C_in, Co, k, w_mode)
-            return e[0]
-        import weakref
-        L = _lib.lib()
-        buf = e[0] if e is not None and e[0].numel() >= nbytes and e[0].device == weight.device else \
-            torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=weight.device)
-        desc = (ctypes.c_longlong * 20)()   # (second descriptor, desc[10:]: unused since the fourth-generation DCN forward left the library)
-        if kind == 'conv':
-            got = L.rvsr_conv2d_pack_weights(_p(weight), C_in, Co, k, w_mode, _p(buf), buf.numel(), desc, _stream())
-        else:
-            got = L.rvsr_dcn_pack_weights(_p(weight), C_in, Co, _p(buf), buf.numel(), desc, _stream())
-        if got == 0:
-            return None
-        self.stats['packs'] += 1
-        self.entries[key] = [buf, weakref.ref(weight), self._version(weight), self.epoch, list(desc[:10]), weight.data_ptr()]
-        self.table = None
-        return buf
-
-    def _verify(self, e, weight, kind, C_in, Co, k, w_mode):
-        """functional._PACK_VERIFY = True (debug): on a cache hit, pack the weight again and compare -- catches writes that bypassed both torch's
-        version counter and repack()/invalidate() (p.data.copy_, raw writes into FlatBuffers.param, EMA swaps)."""
-        L = _lib.lib()
-        tmp = torch.empty_like(e[0])
-        if kind == 'conv':
-            n = L.rvsr_conv2d_pack_weights(_p(weight), C_in, Co, k, w_mode, _p(tmp), tmp.numel(), None, _stream())
-        else:
-            n = L.rvsr_dcn_pack_weights(_p(weight), C_in, Co, _p(tmp), tmp.numel(), None, _stream())
-        n = int(n)
-        if not torch.equal(tmp[:n], e[0][:n]):
-            raise RuntimeError('PackedWeights: stale bf16 weight image (the parameter was written without a version bump; call '
-                               'realvsr_amd.functional.invalidate_weight_cache() after such writes)')
-
-    def repack(self):
-        """Re-pack every live image in one launch (the parameters were just updated in place) and start a new epoch."""
-        self.epoch += 1
-        if not self.enabled or not self.entries:
-            return
-        for k, e in list(self.slices.items()):     # refresh the persistent input-channel slices first: their images are packed below
-            parent = e[2]()
-            if parent is None or e[3] != parent._version or e[5] != parent.data_ptr():
-                del self.slices[k]
-                continue
-            with torch.no_grad():
-                e[0].copy_(parent[:, :k[1]])
-                e[1].copy_(parent[:, k[1]:])
-            e[4] = self.epoch
-        dead = [k for k, e in self.entries.items() if e[1]() is None or e[2] != self._version(e[1]()) or e[5] != e[1]().data_ptr()]
-        for k in dead:
-            del self.entries[k]
-            self.table = None
-        if not self.entries:
-            return
-        by_dev = {}
-        for e in self.entries.values():
-            by_dev.setdefault(e[0].device, []).append(e)
-        if self.table is None:
-            self.table = {}
-            for dev, es in by_dev.items():
-                # PackDesc = two pointers + eight 32-bit fields (48 bytes)
-                raw = torch.empty(len(es), 6, dtype=torch.int64)
-                for i, e in enumerate(es):
-                    d = e[4]
-                    raw[i, 0], raw[i, 1] = d[0], d[1]
-                    for j in range(4):
-                        raw[i, 2 + j] = (d[2 + 2 * j] & 0xffffffff) | ((d[3 + 2 * j] & 0xffffffff) << 32)
-                self.table[dev] = (raw.to(dev), len(es))
-        for dev, es in by_dev.items():
-            tab, n = self.table[dev]
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().rvsr_pack_weights_batched(_p(tab), n, _stream()), 'pack_weights_batched')
-            for e in es:
-                e[3] = self.epoch
-        self.stats['batched'] += 1
-
-
-packed_weights = PackedWeights()
+_PACK_VERIFY = False   # debug (set it from a test): on a cache hit, pack the weight again and compare (caches.PackedWeights.get)
 
 
 def invalidate_weight_cache():
@@ -282,27 +123,56 @@ def invalidate_weight_cache():
     packed_weights.invalidate()
 
 
-def _conv_fwd(L, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, k, stride, w_mode,
-              act, slope, ps, Hout, Wout, what, wparam=None):
-    """rvsr_conv2d_forward with the weight image from the per-step cache when `wparam` (the nn.Parameter behind `weight`,
-    default: none = per-call packing into the shared scratch) lives in FlatBuffers."""
+def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode=0, bias=None, residual=None, out2=None, stride=1,
+          transposed=False, act=ACT_NONE, slope=0.0, pixel_shuffle=False):
+    """rvsr_conv2d_forward (include/realvsr_hip.h section 2) on contiguous [..., C, H, W] tensors, which carry the geometry (leading
+    dimensions fold into the batch): out1 [, out2] = act(conv(cat(x1, x2)) + bias) [+ residual].  transposed: `weight` is
+    (C_in, Co, k, k), used transposed and flipped (a data gradient).  in_mode 2: x1 is stored pixel-shuffled, (B, C1/4, Hs, Ws);
+    pixel_shuffle: out1 is (B, Co/4, 2*Hout, 2*Wout).  The weight image comes from the per-step cache when `weight` lives in FlatBuffers
+    (or is a cached slice of such a parameter), else it is packed per call into the shared scratch."""
+    C1, Hs, Ws = x1.shape[-3:]
+    if in_mode == 2:
+        C1 *= 4
+    C2 = 0 if x2 is None else x2.shape[-3]
+    Co1, Hout, Wout = out1.shape[-3:]
+    B = out1.numel() // (Co1 * Hout * Wout)
+    if pixel_shuffle:
+        Co1, Hout, Wout = Co1 * 4, Hout // 2, Wout // 2
+    Co2 = 0 if out2 is None else out2.shape[-3]
+    k = weight.shape[-1]
+    w_mode = 1 if transposed else 0
+    L = _lib.lib()
     nbytes = L.rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1 + Co2, k)
-    if (_lib.fmt_f16fp8() and k == 3 and stride == 1 and w_mode == 0 and Co1 + Co2 > 32 and not xact and in_mode == 0 and Ws % 4 == 0
-            and (C2 == 0 or C1 % 16 == 0) and ((getattr(x1, 'value', None) or 0) | (getattr(x2, 'value', None) or 0)) % 16 == 0):
+    if (_lib.fmt_f16fp8() and k == 3 and stride == 1 and w_mode == 0 and Co1 + Co2 > 32 and xact is None and in_mode == 0 and Ws % 4 == 0
+            and (C2 == 0 or C1 % 16 == 0) and (x1.data_ptr() | (0 if x2 is None else x2.data_ptr())) % 16 == 0):
         w_mode |= 4     # 'f16fp8' mode: this forward conv in the f16 + fp8 product format (weight image and kernel; _lib.set_gemm_mode)
-    if k == 5 and in_mode == 1:
-        wparam = None   # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused)
-    buf = packed_weights.get(wparam, 'conv', C1 + C2, Co1 + Co2, k, w_mode, nbytes) if wparam is not None else None
+    # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused)
+    buf = None if k == 5 and in_mode == 1 else packed_weights.get(weight, 'conv', C1 + C2, Co1 + Co2, k, w_mode, nbytes)
     if buf is not None:
         ws, w_mode = buf, w_mode | 2
     else:
         ws = _workspace(nbytes, torch.device('cuda', torch.cuda.current_device()))
-    rc = L.rvsr_conv2d_forward(x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, k,
-                               stride, w_mode, act, slope, ps, Hout, Wout, _p(ws), ws.numel(), _stream())
+    rc = L.rvsr_conv2d_forward(_p(x1), C1, _p(x2), C2, _p(xact), xact_slope, in_mode, Hs, Ws, _p(weight), _p(bias), _p(residual),
+                               _p(out1), Co1, _p(out2), Co2, B, k, stride, w_mode, act, slope, int(pixel_shuffle), Hout, Wout,
+                               _p(ws), ws.numel(), _stream())
     if rc == 1 and act == ACT_MASK:     # RVSR_ERR_UNSUPPORTED: the fused gradient mask is an option of one kernel, the caller has a plan B
         return False
     _lib.check(rc, what)
     return True
+
+
+def _conv_wgrad(x1, gout, gw, gb, *, what, x2=None, gact=None, gact_slope=0.0, pixel_shuffled=False, stride=1):
+    """rvsr_conv2d_backward_weight: gw (Co, C1 + C2, k, k) and gb (Co, or None) of the conv of cat(x1, x2) whose output gradient is gout
+    (times act' taken from the saved output `gact`); pixel_shuffled: gout (and gact) are stored (B, Co/4, 2*Hout, 2*Wout)."""
+    C1, H, W = x1.shape[-3:]
+    B, C2 = x1.numel() // (C1 * H * W), (0 if x2 is None else x2.shape[-3])
+    Co, k = gw.shape[0], gw.shape[-1]
+    Gh, Gw = gout.shape[-2:]
+    Ho, Wo = (Gh // 2, Gw // 2) if pixel_shuffled else (Gh, Gw)
+    L = _lib.lib()
+    ws = _workspace(L.rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, k, stride, Ho, Wo), x1.device)
+    _lib.check(L.rvsr_conv2d_backward_weight(_p(x1), C1, _p(x2), C2, H, W, _p(gout), _p(gact), gact_slope, 2 if pixel_shuffled else 0,
+                                             Gh, Gw, _p(gw), _p(gb), Co, B, k, stride, Ho, Wo, 0, _p(ws), ws.numel(), _stream()), what)
 
 
 # ------------------------------------------------------------------------------------------ conv
@@ -342,11 +212,9 @@ class _Conv2dFused(Function):
             out = x1.new_empty(B, Co // 4, 2 * Ho, 2 * Wo)
         else:
             out = x1.new_empty(B, Co, Ho, Wo)
-        L = _lib.lib()
-        _conv_fwd(L, _p(x1), C1, _p(x2), C2, None, 0.0, 0, H, W, _p(weight), _p(bias), _p(residual), _p(out), Co, None, 0, B,
-                  k, stride, 0, act, slope, int(pixel_shuffle), Ho, Wo, 'conv2d_forward', wparam=weight)
-        ctx.cfg = (stride, act, slope, bool(pixel_shuffle), C1, C2, H, W, Ho, Wo, k, bias is not None,
-                   residual is not None)
+        _conv(x1, weight, out, x2=x2, bias=bias, residual=residual, stride=stride, act=act, slope=slope, pixel_shuffle=pixel_shuffle,
+              what='conv2d_forward')
+        ctx.cfg = (stride, act, slope, bool(pixel_shuffle), k, bias is not None, residual is not None)
         ctx.save_for_backward(x1, x2, weight, out if act != ACT_NONE else None)
         ctx.bias_p = bias   # only to find its gradient buffer (_pgrad)
         return out
@@ -355,10 +223,8 @@ class _Conv2dFused(Function):
     @once_differentiable
     def backward(ctx, gout):
         x1, x2, weight, act_out = ctx.saved_tensors
-        stride, act, slope, ps, C1, C2, H, W, Ho, Wo, k, has_bias, has_res = ctx.cfg
+        stride, act, slope, ps, k, has_bias, has_res = ctx.cfg
         gout = gout.contiguous()
-        B, Co = x1.shape[0], weight.shape[0]
-        L = _lib.lib()
         gslope = 0.0 if act == ACT_RELU else slope
         if ctx.grad_premasked:
             act_out = None   # gout arrives multiplied by act'(out) already (the consumer's x_premask)
@@ -379,13 +245,11 @@ class _Conv2dFused(Function):
             masked = False
             if ctx.x_premask is not None:
                 pslope = 0.0 if ctx.x_premask[0] == ACT_RELU else ctx.x_premask[1]
-                masked = _FUSE_GRAD_MASK and k == 3 and _conv_fwd(
-                    L, _p(gout), Co, None, 0, _p(act_out), gslope, in_mode, gout.shape[2], gout.shape[3], _p(weight), None, _p(x1), _p(gx1),
-                    C1, None, 0, B, k, 1, 1, ACT_MASK, pslope, 0, H, W, 'conv2d_backward_data', wparam=weight)
+                masked = _FUSE_GRAD_MASK and k == 3 and _conv(gout, weight, gx1, transposed=True, xact=act_out, xact_slope=gslope, in_mode=in_mode,
+                                                              act=ACT_MASK, slope=pslope, residual=x1, what='conv2d_backward_data')
             if not masked:
-                _conv_fwd(L, _p(gout), Co, None, 0, _p(act_out), gslope, in_mode, gout.shape[2], gout.shape[3], _p(weight), None,
-                          _p(dep), _p(gx1), C1, _p(gx2), C2, B, k, 1, 1, ACT_NONE, 0.0, 0, H, W, 'conv2d_backward_data',
-                          wparam=weight)
+                _conv(gout, weight, gx1, transposed=True, xact=act_out, xact_slope=gslope, in_mode=in_mode, residual=dep, out2=gx2,
+                      what='conv2d_backward_data')
                 if ctx.x_premask is not None:   # no fused epilogue for this frame / GEMM mode: the mask as a separate pass (the producer applies none)
                     gx1.mul_(torch.where(x1 > 0, 1.0, pslope))
             if deposit:   # the first depositor's output IS the sink's buffer (no zero fill); autograd gets no gradient from here
@@ -394,12 +258,8 @@ class _Conv2dFused(Function):
         if need_w or (has_bias and ctx.needs_input_grad[3]):
             gw = _pgrad(weight)
             gb = _pgrad(ctx.bias_p) if has_bias else None
-            nbytes = L.rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, k, stride, Ho, Wo)
-            ws = _workspace(nbytes, x1.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(x1), C1, _p(x2), C2, H, W, _p(gout), _p(act_out), gslope,
-                                                     2 if ps else 0, gout.shape[2], gout.shape[3], _p(gw), _p(gb),
-                                                     Co, B, k, stride, Ho, Wo, 0, _p(ws), ws.numel(), _stream()),
-                       'conv2d_backward_weight')
+            _conv_wgrad(x1, gout, gw, gb, x2=x2, gact=act_out, gact_slope=gslope, pixel_shuffled=ps, stride=stride,
+                        what='conv2d_backward_weight')
         gres = gout if has_res else None
         return gx1, gx2, gw, gb, gres, None, None, None, None, None, None, None, None
 
@@ -418,12 +278,9 @@ class _ResBlockFused(Function):
         B, C, H, W = x.shape
         if w1.shape != (C, C, 3, 3) or w2.shape != (C, C, 3, 3):
             raise RuntimeError('res_block: expected two %dx%dx3x3 convs' % (C, C))
-        L = _lib.lib()
         h, out = torch.empty_like(x), torch.empty_like(x)
-        _conv_fwd(L, _p(x), C, None, 0, None, 0.0, 0, H, W, _p(w1), _p(b1), None, _p(h), C, None, 0, B, 3, 1, 0, ACT_RELU,
-                  0.0, 0, H, W, 'res_block conv1', wparam=w1)
-        _conv_fwd(L, _p(h), C, None, 0, None, 0.0, 0, H, W, _p(w2), _p(b2), _p(x), _p(out), C, None, 0, B, 3, 1, 0, ACT_NONE,
-                  0.0, 0, H, W, 'res_block conv2', wparam=w2)
+        _conv(x, w1, h, bias=b1, act=ACT_RELU, what='res_block conv1')
+        _conv(h, w2, out, bias=b2, residual=x, what='res_block conv2')
         ctx.save_for_backward(x, h, w1, w2)
         ctx.has_bias = (b1 is not None, b2 is not None)
         ctx.bias_p = (b1, b2)   # only to find their gradient buffers (_pgrad)
@@ -434,39 +291,27 @@ class _ResBlockFused(Function):
     def backward(ctx, gout):
         x, h, w1, w2 = ctx.saved_tensors
         gout = gout.contiguous()
-        B, C, H, W = x.shape
-        L = _lib.lib()
         need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad
         gx = gw1 = gb1 = gw2 = gb2 = None
-        nb = L.rvsr_conv2d_wgrad_workspace_bytes(C, 0, C, B, 3, 1, H, W)
         if need_w2 or need_b2:
             gw2 = _pgrad(w2)
             gb2 = _pgrad(ctx.bias_p[1]) if ctx.has_bias[1] else None
-            ws = _workspace(nb, x.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(h), C, None, 0, H, W, _p(gout), None, 0.0, 0, H, W, _p(gw2),
-                                                     _p(gb2), C, B, 3, 1, H, W, 0, _p(ws), ws.numel(), _stream()),
-                       'res_block wgrad2')
+            _conv_wgrad(h, gout, gw2, gb2, what='res_block wgrad2')
         if need_x or need_w1 or need_b1:
             # gradient w.r.t. conv1's output: conv2's data gradient times relu'(h).  The mask is applied in that kernel's epilogue when it
             # has one (8 x 64 tile; one extra read of h instead of a second read of h in BOTH consumers below), else by the consumers.
             gh = torch.empty_like(x)
-            masked = _conv_fwd(L, _p(gout), C, None, 0, None, 0.0, 0, H, W, _p(w2), None, _p(h), _p(gh), C, None, 0, B, 3, 1, 1,
-                               ACT_MASK, 0.0, 0, H, W, 'res_block dgrad2', wparam=w2) if _FUSE_GRAD_MASK else False
+            masked = _FUSE_GRAD_MASK and _conv(gout, w2, gh, transposed=True, act=ACT_MASK, residual=h, what='res_block dgrad2')
             if not masked:
-                _conv_fwd(L, _p(gout), C, None, 0, None, 0.0, 0, H, W, _p(w2), None, None, _p(gh), C, None, 0, B, 3, 1, 1,
-                          ACT_NONE, 0.0, 0, H, W, 'res_block dgrad2', wparam=w2)
-            hmask = None if masked else _p(h)
+                _conv(gout, w2, gh, transposed=True, what='res_block dgrad2')
+            hmask = None if masked else h
             if need_w1 or need_b1:
                 gw1 = _pgrad(w1)
                 gb1 = _pgrad(ctx.bias_p[0]) if ctx.has_bias[0] else None
-                ws = _workspace(nb, x.device)
-                _lib.check(L.rvsr_conv2d_backward_weight(_p(x), C, None, 0, H, W, _p(gh), hmask, 0.0, 0, H, W,
-                                                         _p(gw1), _p(gb1), C, B, 3, 1, H, W, 0, _p(ws), ws.numel(),
-                                                         _stream()), 'res_block wgrad1')
+                _conv_wgrad(x, gh, gw1, gb1, gact=hmask, what='res_block wgrad1')
             if need_x:
                 gx = torch.empty_like(x)
-                _conv_fwd(L, _p(gh), C, None, 0, hmask, 0.0, 0, H, W, _p(w1), None, _p(gout), _p(gx), C, None, 0, B, 3, 1, 1,
-                          ACT_NONE, 0.0, 0, H, W, 'res_block dgrad1', wparam=w1)
+                _conv(gh, w1, gx, transposed=True, xact=hmask, residual=gout, what='res_block dgrad1')
         return gx, gw1, gb1, gw2, gb2
 
 
@@ -498,12 +343,9 @@ class _ConvCatBcast(Function):
         w_a, w_b = packed_weights.split(weight, C1)   # persistent per-step copies when the weight lives in FlatBuffers
         out = x.new_empty(NB, Co, H, W)
         part = x.new_empty(B, Co, H, W)
-        L = _lib.lib()
-        _conv_fwd(L, _p(x), C1, None, 0, None, 0.0, 0, H, W, _p(w_a), _p(bias), None, _p(out), Co, None, 0, NB, 3, 1, 0,
-                  ACT_NONE, 0.0, 0, H, W, 'conv_cat_bcast conv_a', wparam=w_a)
-        _conv_fwd(L, _p(ref), C2, None, 0, None, 0.0, 0, H, W, _p(w_b), None, None, _p(part), Co, None, 0, B, 3, 1, 0,
-                  ACT_NONE, 0.0, 0, H, W, 'conv_cat_bcast conv_b', wparam=w_b)
-        _lib.check(L.rvsr_bcast_add_act(_p(out), _p(part), part.numel(), N, act, slope, _stream()), 'bcast_add_act')
+        _conv(x, w_a, out, bias=bias, what='conv_cat_bcast conv_a')
+        _conv(ref, w_b, part, what='conv_cat_bcast conv_b')
+        _lib.check(_lib.lib().rvsr_bcast_add_act(_p(out), _p(part), part.numel(), N, act, slope, _stream()), 'bcast_add_act')
         ctx.cfg = (N, act, slope, bias is not None)
         ctx.w_ab = (w_a, w_b)   # (python references: the cached slices carry the attribute the weight-image cache keys on)
         # the cached slices are PERSISTENT tensors that repack() / split() overwrite in place, behind save_for_backward's version
@@ -524,17 +366,14 @@ class _ConvCatBcast(Function):
                                    'and its backward')
         N, act, slope, has_bias = ctx.cfg
         gout = gout.contiguous()
-        NB, C1, H, W = x.shape
-        B, C2 = ref.shape[0], ref.shape[1]
-        Co = w_a.shape[0]
-        L = _lib.lib()
+        B, Co = ref.shape[0], w_a.shape[0]
         gslope = 0.0 if act == ACT_RELU else slope
         if ctx.grad_premasked:
             act_out = None
         gx = gref = gw = gb = None
         # gradient of the broadcast partial: sum over the N frames of gout * act'
-        gpart = x.new_empty(B, Co, H, W)
-        _lib.check(L.rvsr_bcast_reduce_act(_p(gout), _p(act_out), _p(gpart), gpart.numel(), N, gslope, _stream()), 'bcast_reduce_act')
+        gpart = x.new_empty(B, Co, *x.shape[2:])
+        _lib.check(_lib.lib().rvsr_bcast_reduce_act(_p(gout), _p(act_out), _p(gpart), gpart.numel(), N, gslope, _stream()), 'bcast_reduce_act')
         x_sink, x_owner, ref_sink, ref_block = ctx.sinks
         # (the reference gradient first: when this conv owns x's sink and ref is a block of x, the deposit must precede the close)
         if ctx.needs_input_grad[1]:
@@ -545,8 +384,7 @@ class _ConvCatBcast(Function):
                     full = ref_sink.buf = ref.new_zeros(ref_sink.shape)
                 blk = full[ref_block * B:(ref_block + 1) * B]
             gref = blk if blk is not None else torch.empty_like(ref)
-            _conv_fwd(L, _p(gpart), Co, None, 0, None, 0.0, 0, H, W, _p(w_b), None, _p(blk), _p(gref), C2, None, 0, B, 3, 1,
-                      1, ACT_NONE, 0.0, 0, H, W, 'conv_cat_bcast dgrad_b', wparam=w_b)
+            _conv(gpart, w_b, gref, transposed=True, residual=blk, what='conv_cat_bcast dgrad_b')
             if blk is not None:
                 gref = None  # deposited into the block of the full tensor's sink
         if ctx.needs_input_grad[0]:
@@ -555,20 +393,14 @@ class _ConvCatBcast(Function):
                 dep = x_sink.close() if x_owner else x_sink.get(x)
             gx = dep if dep is not None else torch.empty_like(x)
             # a fresh sink buffer is all zeros: adding it as the residual is exact and keeps one code path
-            _conv_fwd(L, _p(gout), Co, None, 0, _p(act_out), gslope, 0, H, W, _p(w_a), None, _p(dep), _p(gx), C1, None, 0,
-                      NB, 3, 1, 1, ACT_NONE, 0.0, 0, H, W, 'conv_cat_bcast dgrad_a', wparam=w_a)
+            _conv(gout, w_a, gx, transposed=True, xact=act_out, xact_slope=gslope, residual=dep, what='conv_cat_bcast dgrad_a')
             if dep is not None and not x_owner:
                 gx = None    # deposited: the owner returns the buffer
         if ctx.needs_input_grad[2] or (has_bias and ctx.needs_input_grad[3]):
             gw_a, gw_b = torch.empty_like(w_a), torch.empty_like(w_b)
             gb = w_a.new_empty(Co) if has_bias else None
-            ws = _workspace(L.rvsr_conv2d_wgrad_workspace_bytes(C1, 0, Co, NB, 3, 1, H, W), x.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(x), C1, None, 0, H, W, _p(gout), _p(act_out), gslope, 0, H, W, _p(gw_a),
-                                                     _p(gb), Co, NB, 3, 1, H, W, 0, _p(ws), ws.numel(), _stream()),
-                       'conv_cat_bcast wgrad_a')
-            ws = _workspace(L.rvsr_conv2d_wgrad_workspace_bytes(C2, 0, Co, B, 3, 1, H, W), x.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(ref), C2, None, 0, H, W, _p(gpart), None, 0.0, 0, H, W, _p(gw_b), None,
-                                                     Co, B, 3, 1, H, W, 0, _p(ws), ws.numel(), _stream()), 'conv_cat_bcast wgrad_b')
+            _conv_wgrad(x, gout, gw_a, gb, gact=act_out, gact_slope=gslope, what='conv_cat_bcast wgrad_a')
+            _conv_wgrad(ref, gpart, gw_b, None, what='conv_cat_bcast wgrad_b')
             gw = torch.cat([gw_a, gw_b], 1)
         return gx, gref, gw, gb, None, None, None, None, None, None, None, None
 
@@ -610,77 +442,6 @@ def grad_mask_fusable(H, W):
 
 
 # ------------------------------------------------------------------------------------------ DCN
-class DcnOffsetStats:
-    """Per DCN layer: the sampled offset counters of its last backwards (components beyond 2.5 .. 11.5 px), brought to the host with a
-    non-blocking copy + event, so that a later forward of the layer can pick its LDS tile halo (3 / 7 / 11 px) on the host and launch
-    exactly one kernel.  The forward uses the counters recorded LAG = 3 OPTIMIZER STEPS back (`advance()`, called by FlatAdam.step; the
-    layer's last backward of that step) and waits for that copy: the choice is a function of the data, never of host timing (a
-    query-and-keep-the-old-decision would make the kernel choice, and with it the last bits of the forward, depend on how far the host
-    happens to run ahead), and a host that is up to three steps ahead of the GPU -- which is what absorbs an 80 ms pause of Python's
-    garbage collector, tools/cpu_launch_time.py -- never blocks on it, however many backwards per step a layer has (the per-frame PCD path
-    has N).  Without an optimizer that calls advance() the lag is counted in backwards of the layer instead.  Offsets of a layer change
-    slowly from step to step, and the choice affects speed and the last bits of rounding only (samples beyond the tile gather from global
-    memory with the same rules) -- which also means that data-parallel ranks, whose offsets differ, may run different tile sizes: their
-    forwards are equal to rounding, not bitwise.  Rule = the device-side rule of rvsr_launch_dcn_fwd3: 3 px while < 8 % of the components
-    exceed 3.5 px, 7 px while < 1 % exceed 7.5 px, else 11 px (7 px above 64 output channels)."""
-    LAG = 3
-
-    def __init__(self):
-        self.layers = {}     # id(weight) -> [weakref, ring of [pinned host counters, event, n_samples, tick], records so far, {tick: halo}]
-        self.step = None     # optimizer steps seen (None: nobody advances -- ticks are the layer's own record count)
-
-    def advance(self):
-        self.step = 1 if self.step is None else self.step + 1
-
-    def _tick(self, e):
-        return self.step if self.step is not None else e[2]
-
-    def record(self, weight, probe_dev, nsamples):
-        import weakref
-        e = self.layers.get(id(weight))
-        if e is None or e[0]() is not weight:
-            ring = [[torch.zeros(8, dtype=torch.int32).pin_memory(), torch.cuda.Event(), 0, -1] for _ in range(self.LAG + 1)]
-            e = [weakref.ref(weight), ring, 0, {}]
-            self.layers[id(weight)] = e
-            for k in [k for k, v in self.layers.items() if v[0]() is None]:
-                del self.layers[k]
-        tick = self._tick(e)
-        slot = e[1][tick % (self.LAG + 1)]
-        slot[0].copy_(probe_dev, non_blocking=True)
-        slot[1].record()
-        slot[2] = int(nsamples)
-        slot[3] = tick
-        e[3].pop(tick, None)
-        e[2] += 1
-
-    def forward_halo(self, weight, Co):
-        e = self.layers.get(id(weight))
-        if e is None or e[0]() is not weight or e[2] == 0:
-            return 0
-        want = self._tick(e) - self.LAG
-        # the record of `want`; while the ring fills (or after steps without a backward of this layer): the oldest one it holds
-        live = [s for s in e[1] if s[3] >= 0]
-        older = [s for s in live if s[3] <= want]
-        slot = max(older, key=lambda s: s[3]) if older else min(live, key=lambda s: s[3])
-        tick = slot[3]
-        if tick not in e[3]:
-            c, ev, n = slot[0], slot[1], slot[2]
-            ev.synchronize()
-            if n == 0:
-                halo = 0
-            elif int(c[1]) * 100 < 8 * n:
-                halo = 3
-            elif int(c[3]) * 100 < n or Co > 64:
-                halo = 7
-            else:
-                halo = 11
-            e[3] = {tick: halo}
-        return e[3][tick]
-
-
-dcn_offset_stats = DcnOffsetStats()
-
-
 # ---- the general path of the deformable operator (include/realvsr_hip.h section 1c, csrc/dcn_generic.hip): any kernel size, anisotropic
 # stride / padding / dilation, groups, any channels per deformable group, f32 / f64 / f16.  The fused kernels take the calls they cover.
 _GENERIC_DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2}
@@ -782,13 +543,13 @@ class ModulatedDeformConvFunction(Function):
         if not weight.is_contiguous():
             raise RuntimeError('weight tensor has to be contiguous')     # deform_conv_cuda.cpp:498
         offset, mask = offset.contiguous(), mask.contiguous()
-        ctx.cfg = (stride, padding, dilation, groups, deformable_groups, bias is not None)
         ctx.generic = not _dcn_fused_ok(input, weight, stride, padding, dilation, groups, deformable_groups)
         if ctx.generic:   # any kernel size / anisotropic geometry / groups / f64, f16: the general path (realvsr_hip.h section 1c)
+            ctx.cfg = (stride, padding, dilation, groups, deformable_groups, bias is not None)   # as given: _generic_dcn_backward takes pairs
             ctx.save_for_backward(input, offset, mask, weight, bias)
             return _generic_dcn_forward(input, offset, mask, weight, bias, stride, padding, dilation, groups, deformable_groups)
         stride, padding, dilation = _pair2(stride)[0], _pair2(padding)[0], _pair2(dilation)[0]   # (isotropic here; pairs are accepted)
-        ctx.cfg = (stride, padding, dilation, groups, deformable_groups, bias is not None)
+        ctx.cfg = (stride, padding, dilation, groups, deformable_groups, bias is not None)   # ints: the fused backward
         B, C, H, W = input.shape
         Co, _, kh, kw = weight.shape
         Ho = (H + 2 * padding - (dilation * (kh - 1) + 1)) // stride + 1
@@ -1125,17 +886,13 @@ class _TSATemporalBlock(Function):
         N, B, C, H, W = aligned.shape
         if tuple(w1.shape) != (C, C, 3, 3) or tuple(w2.shape) != (C, C, 3, 3):
             raise RuntimeError('tsa_temporal_block: expected two %dx%dx3x3 convs' % (C, C))
-        L = _lib.lib()
         emb = aligned.new_empty(N, B, C, H, W)
         emb_ref = aligned.new_empty(B, C, H, W)
-        cen = aligned[center]
-        _conv_fwd(L, _p(aligned), C, None, 0, None, 0.0, 0, H, W, _p(w1), _p(b1), None, _p(emb), C, None, 0, N * B, 3, 1, 0,
-                  ACT_NONE, 0.0, 0, H, W, 'tsa tAtt_1', wparam=w1)
-        _conv_fwd(L, _p(cen), C, None, 0, None, 0.0, 0, H, W, _p(w2), _p(b2), None, _p(emb_ref), C, None, 0, B, 3, 1, 0,
-                  ACT_NONE, 0.0, 0, H, W, 'tsa tAtt_2', wparam=w2)
+        _conv(aligned, w1, emb, bias=b1, what='tsa tAtt_1')
+        _conv(aligned[center], w2, emb_ref, bias=b2, what='tsa tAtt_2')
         mod = aligned.new_empty(B, N * C, H, W)
         prob = aligned.new_empty(B, N, H, W)
-        _lib.check(L.rvsr_tsa_temporal_forward(_p(emb), _p(emb_ref), _p(aligned), _p(mod), _p(prob), B, N, C, H, W, 1, _stream()),
+        _lib.check(_lib.lib().rvsr_tsa_temporal_forward(_p(emb), _p(emb_ref), _p(aligned), _p(mod), _p(prob), B, N, C, H, W, 1, _stream()),
                    'tsa_temporal_forward')
         ctx.center = center
         ctx.has_bias = (b1 is not None, b2 is not None)
@@ -1150,32 +907,24 @@ class _TSATemporalBlock(Function):
         N, B, C, H, W = aligned.shape
         center = ctx.center
         gmod = gmod.contiguous()
-        L = _lib.lib()
         galigned, gemb, gemb_ref = torch.empty_like(aligned), torch.empty_like(emb), torch.empty_like(emb_ref)
-        _lib.check(L.rvsr_tsa_temporal_backward(_p(gmod), _p(emb), _p(emb_ref), _p(aligned), _p(prob), _p(galigned), _p(gemb),
-                                                _p(gemb_ref), B, N, C, H, W, 1, _stream()), 'tsa_temporal_backward')
+        _lib.check(_lib.lib().rvsr_tsa_temporal_backward(_p(gmod), _p(emb), _p(emb_ref), _p(aligned), _p(prob), _p(galigned), _p(gemb),
+                                                         _p(gemb_ref), B, N, C, H, W, 1, _stream()), 'tsa_temporal_backward')
         gw1 = gb1 = gw2 = gb2 = None
-        cen = aligned[center]
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             gw1 = _pgrad(w1)
             gb1 = _pgrad(ctx.bias_p[0]) if ctx.has_bias[0] else None
-            ws = _workspace(L.rvsr_conv2d_wgrad_workspace_bytes(C, 0, C, N * B, 3, 1, H, W), aligned.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(aligned), C, None, 0, H, W, _p(gemb), None, 0.0, 0, H, W, _p(gw1), _p(gb1),
-                                                     C, N * B, 3, 1, H, W, 0, _p(ws), ws.numel(), _stream()), 'tsa wgrad tAtt_1')
+            _conv_wgrad(aligned, gemb, gw1, gb1, what='tsa wgrad tAtt_1')
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
             gw2 = _pgrad(w2)
             gb2 = _pgrad(ctx.bias_p[1]) if ctx.has_bias[1] else None
-            ws = _workspace(L.rvsr_conv2d_wgrad_workspace_bytes(C, 0, C, B, 3, 1, H, W), aligned.device)
-            _lib.check(L.rvsr_conv2d_backward_weight(_p(cen), C, None, 0, H, W, _p(gemb_ref), None, 0.0, 0, H, W, _p(gw2), _p(gb2),
-                                                     C, B, 3, 1, H, W, 0, _p(ws), ws.numel(), _stream()), 'tsa wgrad tAtt_2')
+            _conv_wgrad(aligned[center], gemb_ref, gw2, gb2, what='tsa wgrad tAtt_2')
         if ctx.needs_input_grad[0]:
             # galigned += dgrad(tAtt_1)(gemb), in place: the kernel's fused residual is its own output buffer (every lane reads
             # the residual values of exactly the addresses it then stores)
-            _conv_fwd(L, _p(gemb), C, None, 0, None, 0.0, 0, H, W, _p(w1), None, _p(galigned), _p(galigned), C, None, 0,
-                      N * B, 3, 1, 1, ACT_NONE, 0.0, 0, H, W, 'tsa dgrad tAtt_1', wparam=w1)
+            _conv(gemb, w1, galigned, transposed=True, residual=galigned, what='tsa dgrad tAtt_1')
             gcen = galigned[center]
-            _conv_fwd(L, _p(gemb_ref), C, None, 0, None, 0.0, 0, H, W, _p(w2), None, _p(gcen), _p(gcen), C, None, 0, B, 3, 1,
-                      1, ACT_NONE, 0.0, 0, H, W, 'tsa dgrad tAtt_2', wparam=w2)
+            _conv(gemb_ref, w2, gcen, transposed=True, residual=gcen, what='tsa dgrad tAtt_2')
         else:
             galigned = None
         return galigned, None, gw1, gb1, gw2, gb2

@@ -329,3 +329,131 @@ def test_no_matrix_core_instruction_overwrites_its_own_operand():
                           os.path.join(csrc, 'dcn6_kernels.hip')], capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert '0 overlapping' in out.stdout
+
+
+def test_packed_weights_validity_rules_on_cpu():
+    """caches.PackedWeights, what its docstring promises, without a GPU: the three pack entries of the library are replaced by a
+    recorder, the parameters are CPU tensors that carry a `_rvsr_grad_home` as optim.FlatBuffers would give them."""
+    import contextlib
+    import gc
+    import unittest.mock as mock
+    from realvsr_amd import _lib, caches
+
+    calls = []
+
+    class FakeLib:
+        def rvsr_conv2d_pack_weights(self, w, C, Co, k, mode, buf, n, desc, stream):
+            calls.append(('conv', w.value, C, Co, k, mode))
+            if desc is not None:
+                desc[0], desc[1] = w.value, buf.value
+                for i in range(2, 10):
+                    desc[i] = 100 * len(calls) + i
+            return 64
+
+        def rvsr_dcn_pack_weights(self, w, C, Co, buf, n, desc, stream):
+            calls.append(('dcn', w.value, C, Co))
+            assert desc is None or len(desc) == 20      # the library writes 20 values
+            return 64
+
+        def rvsr_pack_weights_batched(self, tab, n, stream):
+            calls.append(('batched', tab.value, n))
+            return 0
+
+    def param(*shape):
+        p = torch.nn.Parameter(torch.randn(*shape))
+        p._rvsr_grad_home = (None, 0, set())
+        return p
+
+    with mock.patch.object(_lib, 'lib', lambda: FakeLib()), mock.patch.object(_lib, 'get_gemm_mode', lambda: 'bf16x3'), \
+            mock.patch.object(caches, '_stream', lambda: None), mock.patch.object(torch.cuda, 'device', lambda d: contextlib.nullcontext()):
+        pw = caches.PackedWeights()
+        pw.enabled = True
+        w, geo = param(8, 4, 3, 3), ('conv', 4, 8, 3, 0, 64)
+        # weights without a home in FlatBuffers are never cached; the f32 mode stages no images at all
+        assert pw.get(torch.nn.Parameter(torch.randn(8, 4, 3, 3)), *geo) is None and not pw.entries and not calls
+        with mock.patch.object(_lib, 'get_gemm_mode', lambda: 'f32'):
+            assert pw.get(w, *geo) is None and not pw.entries
+        # first use packs, the second is a hit on the same buffer
+        b1 = pw.get(w, *geo)
+        assert pw.get(w, *geo) is b1 and pw.stats == {'hits': 1, 'packs': 1, 'batched': 0} and len(calls) == 1
+        assert pw.get(w, 'conv', 4, 8, 3, 1, 64) is not b1 and pw.stats['packs'] == 2      # the transposed image is another entry
+        # an in-place edit under no_grad bumps the version: packed again (into the same buffer)
+        with torch.no_grad():
+            w.mul_(2)
+        assert pw.get(w, *geo) is b1 and pw.stats['packs'] == 3 and pw.stats['hits'] == 1
+        # moved storage, same version: packed again
+        version = w._version
+        w.data = w.data.clone()
+        assert w._version == version
+        pw.get(w, *geo)
+        assert pw.stats['packs'] == 4 and calls[-1][1] == w.data_ptr()
+        # repack(): live entries of unchanged version survive into the new epoch and are the rows of the batched call's table
+        dcn = param(8, 8, 3, 3)
+        assert pw.get(dcn, 'dcn', 8, 8, 3, 0, 64) is not None and pw.stats['packs'] == 5
+        pw.get(w, 'conv', 4, 8, 3, 1, 64)               # (its version is stale since the mul_: packed again)
+        assert pw.stats['packs'] == 6
+        epoch, hits = pw.epoch, pw.stats['hits']
+        pw.repack()
+        assert pw.epoch == epoch + 1 and calls[-1][0] == 'batched' and calls[-1][2] == 3 and pw.stats['batched'] == 1
+        tab, n = pw.table[torch.device('cpu')]
+        assert n == 3 and tab.shape == (3, 6) and tab.dtype == torch.int64 and calls[-1][1] == tab.data_ptr()
+        for row, e in zip(tab.tolist(), pw.entries.values()):   # PackDesc: two pointers, then eight 32-bit fields in pairs
+            d = e.desc
+            assert len(d) == 10 and row == [d[0], d[1]] + [d[2 + 2 * j] | (d[3 + 2 * j] << 32) for j in range(4)]
+        assert tab[0, 0] == w.data_ptr() and tab[0, 1] == b1.data_ptr()
+        npacks = pw.stats['packs']
+        assert pw.get(w, *geo) is b1 and pw.get(dcn, 'dcn', 8, 8, 3, 0, 64) is not None
+        assert pw.stats['hits'] == hits + 2 and pw.stats['packs'] == npacks
+        pw.repack()                                     # nothing added or dropped: the table is kept
+        assert pw.table[torch.device('cpu')][0] is tab and calls[-1] == ('batched', tab.data_ptr(), 3)
+        # repack() drops the entries whose version changed or whose parameter died, and rebuilds the table
+        with torch.no_grad():
+            w.mul_(2)
+        del dcn
+        gc.collect()
+        pw.repack()
+        assert not pw.entries and pw.table is None and pw.stats['batched'] == 2    # (nothing left: no launch)
+        other = param(8, 4, 3, 3)
+        pw.get(w, *geo)
+        pw.get(other, *geo)
+        pw.repack()
+        assert calls[-1][0] == 'batched' and calls[-1][2] == 2
+        del other
+        gc.collect()
+        pw.repack()
+        assert len(pw.entries) == 1 and calls[-1][0] == 'batched' and calls[-1][2] == 1 and pw.table[torch.device('cpu')][1] == 1
+        # split(): the same persistent pair until the parent changes; images are keyed on the slices
+        a, b = pw.split(w, 1)
+        assert a.shape == (8, 1, 3, 3) and b.shape == (8, 3, 3, 3) and a.is_contiguous() and b.is_contiguous()
+        a2, b2 = pw.split(w, 1)
+        assert a2 is a and b2 is b and a._rvsr_parent() is w
+        npacks = pw.stats['packs']
+        ia = pw.get(a, 'conv', 1, 8, 3, 0, 64)
+        assert ia is not None and ia is not b1 and pw.get(a, 'conv', 1, 8, 3, 0, 64) is ia and pw.stats['packs'] == npacks + 1
+        assert calls[-1][:2] == ('conv', a.data_ptr())
+        with torch.no_grad():
+            w.add_(1)                                   # parent edited: same tensors, refreshed in place, their image packed again
+        a3, b3 = pw.split(w, 1)
+        assert a3 is a and b3 is b and torch.equal(a, w[:, :1]) and torch.equal(b, w[:, 1:])
+        assert pw.get(a, 'conv', 1, 8, 3, 0, 64) is ia and pw.stats['packs'] == npacks + 2
+        # repack() refreshes the pair in place from the parameter the optimizer rewrote behind the version counter
+        w.data.mul_(3)
+        assert not torch.equal(a, w[:, :1])
+        pw.repack()
+        assert torch.equal(a, w[:, :1]) and torch.equal(b, w[:, 1:])
+        hits = pw.stats['hits']
+        a4, _ = pw.split(w, 1)
+        assert a4 is a and pw.get(a, 'conv', 1, 8, 3, 0, 64) is ia and pw.stats['hits'] == hits + 1
+        with torch.no_grad():
+            w.add_(1)
+        pw.repack()                                     # a pair whose parent changed version is forgotten; split() starts afresh
+        assert not pw.slices and pw.split(w, 1)[0] is not a
+        # invalidate() forgets everything; a disabled cache returns None / fresh copies
+        pw.get(w, *geo)
+        epoch = pw.epoch
+        pw.invalidate()
+        assert not pw.entries and not pw.slices and pw.table is None and pw.epoch == epoch + 1
+        pw.enabled = False
+        assert pw.get(w, *geo) is None and not pw.entries
+        f1, f2 = pw.split(w, 1), pw.split(w, 1)
+        assert f1[0] is not f2[0] and torch.equal(f1[0], f2[0]) and not pw.slices
