@@ -53,7 +53,7 @@ const char* rvsr_last_error(void);
  *               the input view is one of the vector-staged ones (16-byte aligned, W % 4 == 0);
  *   conv_wgrad2 3x3 stride-1 weight gradient (W_out % 4 == 0, 16-byte aligned);
  *   dcn_fwd3    fused DCN forward with C_out in {64, 128} (3x3, C % 8 == 0);
- *   dcn_bwdin5 / dcn_bwdin6  fused DCN input / offset / mask gradient (3x3, stride 1, C % 8 == 0, C_out <= 128);
+ *   dcn_bwdin6               fused DCN input / offset / mask gradient (3x3, stride 1, C % 8 == 0, C_out <= 128);
  *   dcn_bwdw4 / dcn_bwdw6    fused DCN weight gradient (same gate; bwdw4 also W_out % 4 == 0).
  * Every other kernel (1x1 and strided convs, narrow m-blocks such as the 3-channel output conv, scalar-staged views,
  * the generic DCN path of section 1c) computes three terms in modes 2 / 3, so a network off those shapes gets

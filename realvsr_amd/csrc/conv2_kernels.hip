@@ -1069,10 +1069,10 @@ static int launch_fwd5(const ConvFwdParams& p, hipStream_t st) {
     size_t lds_k = lds;
     if (MT != 2 && p.act == 3) return RVSR_ERR_UNSUPPORTED;   // (mask epilogue: 8 x 64 tile, 64-row m-blocks only)
     if constexpr (MT == 2) {
-        constexpr bool wide_ok = true;   // (the 8 x 64 tile wherever it tiles the frame at least as well as 16 x 32)
+        // (the 8 x 64 tile wherever it tiles the frame at least as well as 16 x 32)
         const long px_n = (long)((p.Hout + 15) / 16 * 16) * ((p.Wout + 31) / 32 * 32), px_w = (long)((p.Hout + 7) / 8 * 8) * ((p.Wout + 63) / 64 * 64);
-        if (p.act == 3 && !(wide_ok && vec == 1 && p.vec4 && px_w <= px_n)) return RVSR_ERR_UNSUPPORTED;   // (mask epilogue: 8 x 64 tile only)
-        if (wide_ok && vec == 1 && p.vec4 && px_w <= px_n) {
+        if (p.act == 3 && !(vec == 1 && p.vec4 && px_w <= px_n)) return RVSR_ERR_UNSUPPORTED;   // (mask epilogue: 8 x 64 tile only)
+        if (vec == 1 && p.vec4 && px_w <= px_n) {
             k = va.act != nullptr ? conv_fwd5_kernel<MT, true, 1, true> : conv_fwd5_kernel<MT, false, 1, true>;
             if (p.fmt) k = conv_fwd5_kernel<MT, false, 1, true, 4>;
             if (nt == 2) k = va.act != nullptr ? conv_fwd5_kernel<MT, true, 1, true, 2> : conv_fwd5_kernel<MT, false, 1, true, 2>;
@@ -1117,17 +1117,11 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspac
     // (the 16-byte-store epilogues address one batch element of the output / residual with 32-bit byte offsets in a 2 GB buffer view)
     p.vec4 = (p.Wout % 4 == 0) && ((((uintptr_t)p.out1) | ((uintptr_t)p.res)) & 15) == 0 && !p.ps && p.out2 == nullptr &&
              sizeof(float) * (size_t)p.Co * p.Hout * p.Wout < ((size_t)1 << 31);
-#define DISPATCH2(KS, S, CCG)                                   \
-    do {                                                        \
-        if (mt == 1) return launch_fwd2<KS, S, 1, CCG>(p, st);  \
-        if (mt == 2) return launch_fwd2<KS, S, 2, CCG>(p, st);  \
-        return launch_fwd2<KS, S, 4, CCG>(p, st);               \
-    } while (0)
+    // (mt is 1 or 2: fwd2_geom)
     if (ksize == 3 && stride == 1) return mt == 1 ? launch_fwd5<1>(p, st) : launch_fwd5<2>(p, st);
-    if (ksize == 3 && stride == 2) DISPATCH2(3, 2, 1);
+    if (ksize == 3 && stride == 2) return mt == 1 ? launch_fwd2<3, 2, 1, 1>(p, st) : launch_fwd2<3, 2, 2, 1>(p, st);
     if (ksize == 5) return stride == 1 ? launch_fwd2<5, 1, 1, 1>(p, st) : launch_fwd2<5, 2, 1, 1>(p, st);
-    DISPATCH2(1, 1, 2);
-#undef DISPATCH2
+    return mt == 1 ? launch_fwd2<1, 1, 1, 2>(p, st) : launch_fwd2<1, 1, 2, 2>(p, st);
 }
 
 // Pre-packed weight images (include/realvsr_hip.h section 2b): the image rvsr_conv2d_forward would build in its workspace,

@@ -429,7 +429,7 @@ int rvsr_launch_dcn_fwd3(const DcnFwdParams& p_in, const void* wpack, int mt, hi
     // gather for all of them, and at one workgroup per CU the large tiles hide that latency worse than the small one -- measured
     // (profiles/r03_notes.md): a 7 px halo with 10 % of the samples outside is slower than the 3 px halo with 65 % outside.
     //   R = 3: < 8 % of the offset components beyond 3.5 px;  R = 7: else, < 1 % beyond 7.5 px (or no larger tile);  R = 11: the rest
-    // (crossovers of the fixed-halo timings at offset std 1.25 / 2.5 / 3.75 / 6.25 px; functional.dcn_forward_halo applies the same rule
+    // (crossovers of the fixed-halo timings at offset std 1.25 / 2.5 / 3.75 / 6.25 px; caches.DcnOffsetStats applies the same rule
     // on the host to the counters of the previous step).
     const unsigned thr3 = (unsigned)(nprobe * 8 / 100) + 1, thr7 = (unsigned)(nprobe / 100) + 1;
     const bool has11 = mt <= 2;

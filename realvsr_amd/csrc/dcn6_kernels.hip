@@ -1,20 +1,39 @@
-// dcn6_kernels.hip -- backward of the modulated DCN, sixth generation (gfx950): dcn_bwdin6 (input / offset / mask gradient).
+// dcn6_kernels.hip -- backward of the modulated DCN, sixth generation (gfx950): dcn_bwdin6 (input / offset / mask gradient) and, further
+// down, dcn_bwdw6 (weight / bias gradient).
 //
-// Replaces dcn_bwdin5 (dcn5_kernels.hip; the reference's modulated_deformable_col2im + col2im_coord pair, kernel.cu:636-767, with the
-// `columns = W^T gOut` GEMM of deform_conv_cuda.cpp:623-626 in front of them) where 8 divides the channels per deformable group.
+// dcn_bwdin6 replaces the reference's modulated_deformable_col2im + col2im_coord pair (kernel.cu:636-767) together with the
+// `columns = W^T gOut` GEMM of deform_conv_cuda.cpp:623-626 in front of them, where 8 divides the channels per deformable group; every other
+// call takes the first-generation dcn_bwd_input_kernel (dcn_kernels.hip).  Workgroup = 8 waves = 8 rows x 32 pixels, K chunk = 8 input channels.
 //
-// Why (profiles/r04_*, r05_notes.md): dcn_bwdin5 executed 1.06 G vector wave-instructions per L1 launch against the forward's 0.24 G --
-// 200 per (wave, tap) -- and half of them were forced by its lane layout: the accumulator registers of lane (pixel, half) held 4 channels
-// of FOUR taps, so both halves of a wave computed every sampling geometry, every tap needed three partner-lane sums
-// (v_permlane32_swap + nops) for grad_offset / grad_mask, and each lane carried four channels through scalar f32 arithmetic.  Here
+// The scatter window (from the fifth generation, dcn_bwdin5; micro-benchmarks of the LDS on the MI355X: tools/micro/, profiles/r03_notes.md),
+// cycles per wave instruction per CU with 8 waves issuing:
+//     ds_add_u32 3.7    ds_add_u64 5.6    ds_add_f64 7.3    ds_add_f32 169 (!)    128-bit read-modify-write pair 15-23,
+//     the same whether 16 or 64 lanes are active; with the address pattern of this scatter at sub-pixel offsets of random sign
+//     (neighbouring lanes land on the same or the neighbouring cell): ds_add_u32 5.9, ds_add_u64 11.3, ds_add_f64 19.7.
+//   * The grad_input tile of a workgroup is ONE shared window of 32-bit FIXED-POINT cells that every lane updates with ds_add_u32: no
+//     ownership, no parity passes, no claims, no merge, any offset pattern.  Integer addition is associative: the in-tile sum is
+//     bit-reproducible whatever the order.
+//     Scale: a contribution is w_corner * mask * col_grad with w, mask in [0, 1] and |col_grad[t, c, px]| = |<W[:, c, t], gOut[:, px]>|
+//     <= ||W[:, c, t]||_2 * ||gOut[:, px]||_2 (Cauchy-Schwarz); with Wn = the largest column norm of the chunk (dcn_bwd5_wnorm_kernel) and
+//     Gn = the largest pixel norm of the tile (prologue), S = 2^31 / (2304 * Wn * Gn) maps every contribution to |q| <= 2^19.8 and a cell
+//     can receive at most 8 * 32 * 9 = 2304 of them per chunk (each (pixel, tap) at most once): NO overflow for any input.
+//     One unit is ~1e-6 of the bound, round-to-nearest (magic-number add), so the quantisation noise of a cell (~6 units at 36
+//     contributions) stays below the bf16x3 error of col_grad itself; measured against the f64 oracle in tests/test_gpu_dcn*.py.
+//   * 4 B per (cell, channel): the halo R is a template parameter, R = 2 / 4 / 5 / 8 / 12 px around the 8 x 32 pixel tile, selected on the
+//     device from the offsets (dcn_offset_probe2_kernel).  Samples beyond the window keep the global gather / atomic path.
+//   * Co > 64 runs in ONE pass: the K loop of col_grad = W^T gOut covers all output channels (NK = 8 k-steps: 64 VGPRs of gOut fragments, a
+//     48 KB weight block per chunk), so sampling, scatter, flush and the offset / mask stores are done once.
+//
+// What the sixth generation changed (profiles/r04_*, r05_notes.md): dcn_bwdin5 executed 1.06 G vector wave-instructions per L1 launch against
+// the forward's 0.24 G -- 200 per (wave, tap) -- and half of them were forced by its lane layout: the accumulator registers of lane
+// (pixel, half) held 4 channels of FOUR taps, so both halves of a wave computed every sampling geometry, every tap needed three partner-lane
+// sums (v_permlane32_swap + nops) for grad_offset / grad_mask, and each lane carried four channels through scalar f32 arithmetic.  Here
 //   * the M rows of col_grad = W^T gOut are PERMUTED in the packed weight image so that lane (pixel, half) holds all 8 channels of TWO
 //     taps: a lane owns a whole (pixel, tap) -- one geometry per lane, no partner-lane sums, every lane stores its own grad_offset /
 //     grad_mask -- and the halves of a wave work on different taps: 5 lane iterations per chunk instead of 9 taps;
 //   * the per-channel arithmetic runs on channel PAIRS (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 with op_sel broadcasts);
 //   * the main path of a lane iteration is branch-free (dead lanes add 0 to spread cells and store beyond the buffer view); samples
-//     beyond the window take a rolled loop over the channels (global gather / atomics with the reference's rule set).
-// Everything else is dcn_bwdin5's: one shared LDS window of 32-bit fixed-point cells, ds_add_u32 from every lane, scale from
-// Cauchy-Schwarz norms (no overflow for any input), flushed with one f32 global atomic per touched cell; halo selected on the device.
+//     beyond the window take the global gather / atomics with the reference's rule set.
 //
 // (A fully fused backward -- this kernel plus the weight gradient from the same sampling pass, column values transposed by the matrix
 // core -- is numerically right and kept as experiments/dcn_bwd6_fused.hip; it needs ~400 live registers per wave and ran 16 ms per L1
@@ -39,6 +58,36 @@ extern "C" int rvsr_debug_read_dcn6(unsigned long long* out) { return (int)hipMe
 __host__ __device__ __forceinline__ int bwd6_tap(int it, int h) {
     return h == 0 ? (it == 0 ? 0 : it == 1 ? 1 : it == 2 ? 4 : it == 3 ? 2 : it == 4 ? 8 : -1)
                   : (it == 0 ? 3 : it == 1 ? 6 : it == 2 ? 7 : it == 3 ? 5 : -1);
+}
+
+// Wn[chunk] for the fixed-point scale: one block per chunk, 576 threads = 72 (tap, channel) columns x 8 slices of the output
+// channels; slice sums combined through LDS, then the maximum over the columns
+__global__ __launch_bounds__(576) void dcn_bwd5_wnorm_kernel(const float* __restrict__ w, float* __restrict__ wn, int Co, int C) {
+    __shared__ float red[576];
+    const int chunk = blockIdx.x, t = threadIdx.x, col = t % 72, sl = t / 72;
+    const int tap = col >> 3, c = 8 * chunk + (col & 7);
+    float s = 0.f;
+    if (c < C)
+        for (int o = sl; o < Co; o += 8) {
+            const float v = w[((size_t)o * C + c) * 9 + tap];
+            s += v * v;
+        }
+    red[t] = s;
+    __syncthreads();
+    if (t < 72) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a += red[t + 72 * k];
+        red[t] = a;
+    }
+    __syncthreads();
+    if (t < 64) red[t] = fmaxf(red[t], t + 64 < 72 ? red[t + 64] : 0.f);
+    __syncthreads();
+    for (int k = 32; k > 0; k >>= 1) {
+        if (t < k) red[t] = fmaxf(red[t], red[t + k]);
+        __syncthreads();
+    }
+    if (t == 0) wn[chunk] = sqrtf(red[0]);
 }
 
 // packed[chunk][mt (3)][part (hi, lo)][o-octet (2 NK)][row (32)][8 o].  Row i of M tile mt lands in accumulator register
@@ -104,7 +153,9 @@ __device__ __forceinline__ f32x2 pk_mul_y(f32x2 s, f32x2 b) {
 __device__ __forceinline__ void lds_add_i32_6(int* p, int v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_u32
 }
-// a + b of the two lane halves in every lane (see dcn5_kernels.hip: half_sum)
+// a + b of the two lane halves in every lane: v_permlane32_swap a, b exchanges lanes 32..63 of a with lanes 0..31 of b; with a = b = v every
+// lane then holds both halves' values (VALU, no LDS queue).  Inline assembly: this hipcc lowers the second result of
+// __builtin_amdgcn_permlane32_swap to a copy of the first; the s_nop covers the VALU-write -> permlane-read distance by hand.
 __device__ __forceinline__ float half_sum6(float v) {
     float a = v, b = v;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
@@ -377,7 +428,7 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
         bf16x8* const wcur = wsb + (W2 ? (chunk & 1) * 3 * WBLK : 0);
         if (W2 && !(RVSR_ABL6 & 32)) request_weights(cn, wsb + ((chunk + 1) & 1) * 3 * WBLK);   // (the other buffer: read by chunk - 1, whose iterations are behind the barrier)
 
-        // fixed-point scale of this chunk (dcn5_kernels.hip header): |contribution| * S <= 0.995 * 2^31 / 2304
+        // fixed-point scale of this chunk (file header): |contribution| * S <= 0.995 * 2^31 / 2304
         float S, invS;
         {
             float g2 = gn_red[0];
@@ -592,14 +643,75 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
     TS6(9);
 }
 
-// (dcn5_kernels.hip)
-__global__ void dcn_bwd5_wnorm_kernel(const float* __restrict__ w, float* __restrict__ wn, int Co, int C);
+// Sampled statistic behind the halo selection of both DCN directions: every 16th row of every offset plane;
+// cnt[0..5] = components with |v| > 2.5 / 3.5 / 5.5 / 7.5 / 8.5 / 11.5 px (DcnHaloSel).
+__global__ void dcn_offset_probe2_kernel(const float* __restrict__ off, size_t off_bs, int B, int planes, int Ho, int Wo,
+                                         unsigned* __restrict__ cnt) {
+    const int nrow = (Ho + 15) / 16;
+    const size_t total = (size_t)B * planes * nrow * Wo;
+    const float lim[DCN_PROBE_COUNTERS] = {2.5f, 3.5f, 5.5f, 7.5f, 8.5f, 11.5f};
+    unsigned n[DCN_PROBE_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wo);
+        size_t r = i / Wo;
+        const int row = (int)(r % nrow);
+        r /= nrow;
+        const int pl = (int)(r % planes), b = (int)(r / planes);
+        const int y = row * 16 + 8 < Ho ? row * 16 + 8 : Ho - 1;
+        const float v = fabsf(off[(size_t)b * off_bs + ((size_t)pl * Ho + y) * Wo + x]);
+#pragma unroll
+        for (int k = 0; k < DCN_PROBE_COUNTERS; ++k) n[k] += v > lim[k] ? 1u : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < DCN_PROBE_COUNTERS; ++k)
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) n[k] += __shfl_xor(n[k], s);
+    // one atomic per counter and BLOCK (per wave, 2 K blocks x 4 waves on the same few addresses took 226 us at 3 px offsets)
+    __shared__ unsigned part[DCN_PROBE_COUNTERS][4];
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < DCN_PROBE_COUNTERS; ++k) part[k][wv] = n[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < DCN_PROBE_COUNTERS) {
+        const unsigned t = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+        if (t) atomicAdd(cnt + threadIdx.x, t);
+    }
+}
+
+static size_t dcn_probe_samples(const DcnGeom& d) { return (size_t)d.B * ((d.C / d.cpg) * 18) * ((d.Ho + 15) / 16) * d.Wo; }
+// memset-free: the caller zeroes the counters (a fresh torch.zeros in the Python layer, hipMemsetAsync in the backward's own path)
+size_t rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st) {
+    const int oplanes = (d.C / d.cpg) * 18;
+    const size_t nprobe = dcn_probe_samples(d);
+    const unsigned nb = (unsigned)((nprobe + 2047) / 2048 < 2048 ? (nprobe + 2047) / 2048 : 2048);
+    hipLaunchKernelGGL(dcn_offset_probe2_kernel, dim3(nb ? nb : 1), dim3(256), 0, st, d.offset, d.off_bs, d.B, oplanes, d.Ho, d.Wo, cnt);
+    return nprobe;
+}
+
+// One batch element's planes are addressed with 32-bit byte offsets (x through a 2 GB view: bit 31 marks the zero padding).
+static bool dcn_planes_below_2g(const DcnGeom& d) {
+    const size_t oplanes = (size_t)(d.C / d.cpg) * 18, planes = oplanes > (size_t)d.C ? oplanes : (size_t)d.C, lim = (size_t)1 << 31;
+    return planes * (size_t)d.H * d.W * sizeof(float) < lim && planes * (size_t)d.Ho * d.Wo * sizeof(float) < lim;
+}
+// The geometries dcn_bwdin6 takes; every other call takes the first-generation dcn_bwd_input_kernel.
+bool rvsr_dcn_bwdin6_takes(const DcnGeom& d) {
+    return d.cpg % 8 == 0 && d.C % 8 == 0 && d.stride == 1 && d.dil == 1 && d.Co <= 128 && dcn_planes_below_2g(d);
+}
 
 static int nk6_of(int Co) { return Co <= 16 ? 1 : (Co <= 32 ? 2 : (Co <= 64 ? 4 : 8)); }
-size_t rvsr_dcn_bwdin6_workspace_bytes(int Co, int C) {
-    // weight image + per-chunk column norms + the probe's counters
-    return (size_t)((C + 7) / 8) * 3 * 2 * (2 * nk6_of(Co)) * 32 * 16 + (((size_t)((C + 7) / 8) * 4 + 255) & ~(size_t)255) + 256;
+// dcn_bwdin6's share of the backward's workspace, byte offsets: the packed weight image at 0, the per-chunk column norms, the probe's counters
+struct Bwdin6Workspace { size_t wnorm, probe, total; };
+static Bwdin6Workspace bwdin6_workspace(int Co, int C) {
+    const size_t nchunks = (size_t)((C + 7) / 8);
+    Bwdin6Workspace w;
+    w.wnorm = nchunks * 3 * 2 * (2 * nk6_of(Co)) * 32 * 16;
+    w.probe = w.wnorm + ((nchunks * 4 + 255) & ~(size_t)255);
+    w.total = w.probe + 256;
+    return w;
 }
+size_t rvsr_dcn_bwdin6_workspace_bytes(int Co, int C) { return bwdin6_workspace(Co, C).total; }
 
 template <int NK, int R>
 static int launch_bwdin6(const DcnBwdIn6Params& p, const bf16x8* wpack, hipStream_t st) {
@@ -640,22 +752,17 @@ static int launch_bwdin6_halo(const DcnBwdIn6Params& p, const bf16x8* wpack, int
     return launch_bwdin6<NK, 8>(p, wpack, st);
 }
 
-// halo < 0: selected on the device from the offsets (probe + one launch per candidate halo, no host round trip); same protocol as
-// rvsr_launch_dcn_bwdin5, which stays the kernel of geometries this one does not cover (RVSR_ERR_UNSUPPORTED).
+// halo < 0: selected on the device from the offsets (probe + one launch per candidate halo, no host round trip).
+// RVSR_ERR_UNSUPPORTED (geometry not taken, or no workspace): the caller falls back to the first-generation kernel.
 int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
                            float* gmask, size_t gmask_bs, void* workspace, size_t workspace_bytes, hipStream_t st, int halo,
                            const unsigned* probe_in, void* agt) {
-    if (d.cpg % 8 != 0 || d.C % 8 != 0 || d.stride != 1 || d.dil != 1 || d.Co > 128) return RVSR_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < rvsr_dcn_bwdin6_workspace_bytes(d.Co, d.C)) return RVSR_ERR_UNSUPPORTED;
-    // 32-bit byte offsets into one batch element's planes (x through a 2 GB view: bit 31 marks the zero padding)
-    const size_t planes = (size_t)(d.C / d.cpg) * 18 > (size_t)d.C ? (size_t)(d.C / d.cpg) * 18 : (size_t)d.C;
-    if (planes * (size_t)d.H * d.W * sizeof(float) >= ((size_t)1 << 31) || planes * (size_t)d.Ho * d.Wo * sizeof(float) >= ((size_t)1 << 31))
-        return RVSR_ERR_UNSUPPORTED;
+    const Bwdin6Workspace lay = bwdin6_workspace(d.Co, d.C);
+    if (!rvsr_dcn_bwdin6_takes(d) || !workspace || workspace_bytes < lay.total) return RVSR_ERR_UNSUPPORTED;
     const int NK = nk6_of(d.Co), nchunks = (d.C + 7) / 8;
-    const size_t wbytes = (size_t)nchunks * 3 * 2 * (2 * NK) * 32 * 16;
     bf16x8* wpack = (bf16x8*)workspace;
-    float* wnorm = (float*)((unsigned char*)workspace + wbytes);
-    unsigned* cnt = (unsigned*)((unsigned char*)workspace + wbytes + (((size_t)nchunks * 4 + 255) & ~(size_t)255));
+    float* wnorm = (float*)((unsigned char*)workspace + lay.wnorm);
+    unsigned* cnt = (unsigned*)((unsigned char*)workspace + lay.probe);
     hipLaunchKernelGGL(dcn_bwd5_wnorm_kernel, dim3(nchunks), dim3(576), 0, st, weight, wnorm, d.Co, d.C);
     const size_t total = (size_t)nchunks * 3 * (2 * NK) * 32;
     const dim3 pg((unsigned)((total + 255) / 256)), pb(256);
@@ -681,8 +788,7 @@ int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g
         BWDIN6_DISPATCH(halo);
         return rc;
     }
-    const int oplanes = (d.C / d.cpg) * 18, nrow = (d.Ho + 15) / 16;
-    const size_t nprobe = (size_t)d.B * oplanes * nrow * d.Wo;
+    const size_t nprobe = dcn_probe_samples(d);
     if (probe_in != nullptr) {
         cnt = const_cast<unsigned*>(probe_in);   // the forward of this layer already counted these offsets (rvsr_dcn_pack_forward's probe)
     } else {
@@ -1026,7 +1132,7 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
     }
 }
 
-// streams (= partials) of a launch with `wpc` workgroups per CU; 0: geometry not covered
+// streams (= partials) of a launch with `wpc` workgroups per CU; 0: more (chunk, 64 output channels) units than the 256 CUs, not covered
 static int bwdw6_streams(int Co, int C, int wpc, int* nmb_out, int* xcd_out) {
     const int nchunks = C / 8, nmb = (Co + 63) / 64, U = nchunks * nmb;
     if (U <= 0 || U > 256) return 0;
@@ -1048,6 +1154,13 @@ size_t rvsr_dcn_bwdw6_workspace_bytes(int Co, int C) {
 // the operand buffer dcn_bwdin6 writes for dcn_bwdw6: one 16-byte vector per (row, x tile, 32 output channels, k-step, hi / lo, lane)
 size_t rvsr_dcn_bwd6_agt_bytes(int B, int Co, int Ho, int Wo) {
     return (size_t)B * (((Ho + 7) / 8) * 8) * ((Wo + 31) / 32) * (size_t)(2 * ((Co + 63) / 64)) * 4 * 64 * 16;
+}
+
+// The geometries dcn_bwdw6 takes: dcn_bwdin6's (which writes its gOut operand), at most 256 units, and 32-bit byte offsets into the 64
+// gOut planes of a unit.  Every other call takes dcn_bwdw2 / dcn_bwdw4.
+bool rvsr_dcn_bwdw6_takes(const DcnGeom& d) {
+    return rvsr_dcn_bwdin6_takes(d) && bwdw6_streams(d.Co, d.C, 1, nullptr, nullptr) > 0 &&
+           (size_t)64 * d.Ho * d.Wo * sizeof(float) < ((size_t)1 << 31);
 }
 
 template <int R, int TH>
@@ -1073,16 +1186,11 @@ static int launch_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb,
 
 // gw / gb are ACCUMULATED into (the reference's convention, cpp:659-671).  RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdw4.
 int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (d.cpg % 8 != 0 || d.C % 8 != 0 || d.stride != 1 || d.dil != 1 || d.Co > 128 || agt == nullptr) return RVSR_ERR_UNSUPPORTED;
+    if (!rvsr_dcn_bwdw6_takes(d) || agt == nullptr) return RVSR_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < rvsr_dcn_bwdw6_workspace_bytes(d.Co, d.C)) return RVSR_ERR_UNSUPPORTED;
     int nmb = 0, xcd = 0;
     const int wpc = bwdw6_wpc();
     const int ns = bwdw6_streams(d.Co, d.C, wpc, &nmb, &xcd);
-    if (ns <= 0 || !workspace || workspace_bytes < rvsr_dcn_bwdw6_workspace_bytes(d.Co, d.C)) return RVSR_ERR_UNSUPPORTED;
-    // 32-bit byte offsets into one batch element's planes
-    const size_t planes = (size_t)(d.C / d.cpg) * 18 > (size_t)d.C ? (size_t)(d.C / d.cpg) * 18 : (size_t)d.C;
-    if (planes * (size_t)d.H * d.W * sizeof(float) >= ((size_t)1 << 31) || planes * (size_t)d.Ho * d.Wo * sizeof(float) >= ((size_t)1 << 31) ||
-        (size_t)64 * d.Ho * d.Wo * sizeof(float) >= ((size_t)1 << 31))
-        return RVSR_ERR_UNSUPPORTED;
     if (wpc == 2) return launch_bwdw6<2, 4>(d, agt, gw, gb, workspace, ns, nmb, xcd, st);
     return launch_bwdw6<4, 8>(d, agt, gw, gb, workspace, ns, nmb, xcd, st);
 }

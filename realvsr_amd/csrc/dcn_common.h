@@ -110,25 +110,25 @@ int rvsr_launch_dcn_fwd2(const DcnFwdParams& p, void* workspace, size_t workspac
 // third-generation forward (dcn3_kernels.hip): consumes the weight image rvsr_launch_dcn_fwd2 packs; stride 1, dilation 1
 int rvsr_launch_dcn_fwd3(const DcnFwdParams& p, const void* wpack, int mt, hipStream_t st, const unsigned* probe = nullptr, size_t nprobe = 0,
                          int halo_hint = 0);
-// the three-counter offset statistic both DCN directions select their tile halo from (dcn5_kernels.hip); returns the sample count
+// the sampled offset statistic both DCN directions select their tile halo from (dcn6_kernels.hip); returns the sample count
 size_t rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st);
 int rvsr_launch_dcn_bwdw2(const DcnGeom& d, const TView& g, float* part, float* bpart_or_null, int P, int nty, int gy, int gz,
                           hipStream_t st);
-// sixth-generation input / offset / mask gradient (dcn6_kernels.hip): dcn_bwdin5's window with a lane = (pixel, tap) layout and packed math;
-// same calling protocol.  RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdin5.
+// Sixth-generation backward (dcn6_kernels.hip).  The two predicates are the only statement of what the kernels take: the launchers, the
+// backward's dispatcher and its workspace query all go through them.
+//   rvsr_dcn_bwdin6_takes: 8 | channels per deformable group, 8 | C, stride 1, dilation 1, Co <= 128, one batch element's planes below 2 GB;
+//   rvsr_dcn_bwdw6_takes:  the same, plus at most 256 (8-channel chunk, 64 output channels) units and 64 gOut planes below 2 GB.
+bool rvsr_dcn_bwdin6_takes(const DcnGeom& d);
+bool rvsr_dcn_bwdw6_takes(const DcnGeom& d);
+// input / offset / mask gradient: one shared fixed-point LDS window per workgroup, lane = (pixel, tap), packed math; halo < 0 = window chosen
+// on the device.  RVSR_ERR_UNSUPPORTED (not taken, or no workspace): the caller falls back to the first-generation dcn_bwd_input_kernel.
 size_t rvsr_dcn_bwdin6_workspace_bytes(int Co, int C);
 int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
                            float* gmask, size_t gmask_bs, void* workspace, size_t workspace_bytes, hipStream_t st, int halo = -1,
                            const unsigned* probe_in = nullptr, void* agt = nullptr);
-// sixth-generation weight / bias gradient (dcn6_kernels.hip): column values transposed by the matrix core, chunk-major persistent; gw / gb
-// accumulated into.  RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdw4.
+// weight / bias gradient: column values transposed by the matrix core, chunk-major persistent; gw / gb accumulated into.
+// RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdw2 / dcn_bwdw4.
 // Its gOut operand comes pre-transposed from dcn_bwdin6 (`agt`, rvsr_dcn_bwd6_agt_bytes): the two run as a pair.
 size_t rvsr_dcn_bwdw6_workspace_bytes(int Co, int C);
 size_t rvsr_dcn_bwd6_agt_bytes(int B, int Co, int Ho, int Wo);
 int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb, void* workspace, size_t workspace_bytes, hipStream_t st);
-// fifth-generation input / offset / mask gradient (dcn5_kernels.hip): shared f64 LDS window; halo < 0 = chosen on the device
-size_t rvsr_dcn_bwdin5_workspace_bytes(int Co, int C);
-int rvsr_launch_dcn_bwdin5(const DcnGeom& d, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
-                           float* gmask, size_t gmask_bs, void* workspace, size_t workspace_bytes, hipStream_t st, int halo = -1,
-                           const unsigned* probe_in = nullptr);
-

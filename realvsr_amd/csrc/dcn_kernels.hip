@@ -21,6 +21,8 @@
 // explicit and the mask sigmoid (deform_conv.py:281-283) is then applied in-kernel.
 #include "rvsr_common.h"
 
+#include <string.h>
+
 #include "dcn_common.h"
 
 // Build the column tile of channel chunk [c0, c0+8) for the 128 pixels of a tile.
@@ -427,14 +429,6 @@ extern "C" size_t rvsr_modulated_deform_conv_forward_workspace_bytes(int channel
     return rvsr_dcn_fwd2_workspace_bytes(channels_out, channels);
 }
 
-// Can the dcn_bwdin6 / dcn_bwdw6 pair take a call of this geometry?  (The workspace query has no deformable_groups argument: the offset planes of
-// one batch element are bounded by their worst case, 18 planes per 8 channels; rvsr_launch_dcn_bwdin6 repeats the exact test.)  The query sizes the
-// hand-off buffer and the backward offers it to the pair by this one predicate.
-static bool dcn_bwd6_pair_possible(int channels, int height, int width, int channels_out, int stride, int dil) {
-    const size_t planes = (size_t)(channels / 8) * 18 > (size_t)channels ? (size_t)(channels / 8) * 18 : (size_t)channels;
-    return stride == 1 && dil == 1 && channels % 8 == 0 && channels_out <= 128 &&
-           planes * (size_t)height * width * sizeof(float) < ((size_t)1 << 31);
-}
 // everything but the operand buffer dcn_bwdin6 hands to dcn_bwdw6 (that buffer sits behind it, 256-byte aligned)
 static size_t dcn_backward_workspace_base(int batch, int channels, int height, int width, int channels_out, int stride, int pad, int dil) {
     const int Ho = (height + 2 * pad - (dil * 2 + 1)) / stride + 1, Wo = (width + 2 * pad - (dil * 2 + 1)) / stride + 1;
@@ -442,21 +436,36 @@ static size_t dcn_backward_workspace_base(int batch, int channels, int height, i
     const int gy = (channels_out + 63) / 64, gz = (channels + DCN_CC - 1) / DCN_CC;
     const size_t Q = 8 * (size_t)bww_P(ntiles, gy, gz);
     const size_t a = sizeof(float) * Q * ((size_t)channels_out * channels * 9 + channels_out);
-    size_t b2 = rvsr_dcn_bwdin5_workspace_bytes(channels_out, channels);   // weight image + column norms + the probe counters
-    const size_t b6 = rvsr_dcn_bwdin6_workspace_bytes(channels_out, channels);
-    if (b6 > b2) b2 = b6;
+    const size_t b6 = rvsr_dcn_bwdin6_workspace_bytes(channels_out, channels);   // weight image + column norms + the probe counters
     const size_t w6 = rvsr_dcn_bwdw6_workspace_bytes(channels_out, channels);
-    if (w6 > b2) b2 = w6;
-    return ((a > b2 ? a : b2) + 255) & ~(size_t)255;
+    const size_t m = a > b6 ? (a > w6 ? a : w6) : (b6 > w6 ? b6 : w6);
+    return (m + 255) & ~(size_t)255;
+}
+// Bytes of the gOut^T hand-off of the dcn_bwdin6 / dcn_bwdw6 pair behind that base (hi + lo bf16 copy of gOut, 8-row x 32-column tiles: ~575 MiB
+// at B = 40, Co = 64, 180 x 320); 0: none.  The workspace query has no deformable_groups argument, so it asks rvsr_dcn_bwdw6_takes about the
+// call with the MOST offset planes a batch element can have, one deformable group per 8 channels: an upper bound of the planes, hence a buffer
+// only where dcn_bwdw6 takes the call whatever its grouping.  The backward offers the buffer where this is non-zero AND the call itself is taken.
+static size_t dcn_bwd6_handoff_bytes(int batch, int channels, int height, int width, int channels_out, int stride, int pad, int dil) {
+    DcnGeom d = {};
+    d.B = batch; d.C = channels; d.H = height; d.W = width; d.Co = channels_out; d.stride = stride; d.pad = pad; d.dil = dil;
+    d.Ho = (height + 2 * pad - (dil * 2 + 1)) / stride + 1; d.Wo = (width + 2 * pad - (dil * 2 + 1)) / stride + 1;
+    d.cpg = 8; d.dg = channels / 8;
+    return rvsr_dcn_bwdw6_takes(d) ? rvsr_dcn_bwd6_agt_bytes(batch, channels_out, d.Ho, d.Wo) : 0;
 }
 extern "C" size_t rvsr_modulated_deform_conv_backward_workspace_bytes(int batch, int channels, int height, int width,
                                                                       int channels_out, int stride, int pad, int dil) {
-    const int Ho = (height + 2 * pad - (dil * 2 + 1)) / stride + 1, Wo = (width + 2 * pad - (dil * 2 + 1)) / stride + 1;
-    size_t n = dcn_backward_workspace_base(batch, channels, height, width, channels_out, stride, pad, dil);
-    // the gOut^T hand-off of the dcn_bwdin6 / dcn_bwdw6 pair (hi + lo bf16 copy of gOut, 8-row x 32-column tiles: ~575 MiB at B = 40, Co = 64,
-    // 180 x 320): only for calls that pair can take
-    if (dcn_bwd6_pair_possible(channels, height, width, channels_out, stride, dil)) n += rvsr_dcn_bwd6_agt_bytes(batch, channels_out, Ho, Wo);
-    return n;
+    return dcn_backward_workspace_base(batch, channels, height, width, channels_out, stride, pad, dil) +
+           dcn_bwd6_handoff_bytes(batch, channels, height, width, channels_out, stride, pad, dil);
+}
+
+// RVSR_DCN_BWD (developer A/B switch, read once): unset or 7 = dcn_bwdin6 + dcn_bwdw6 (1), 64 = dcn_bwdin6 + dcn_bwdw4 (0); anything else is
+// refused (-1) rather than ignored
+static int dcn_bwd_pair_switch() {
+    static const int v = [] {
+        const char* e = getenv("RVSR_DCN_BWD");
+        return !e || !strcmp(e, "7") ? 1 : (!strcmp(e, "64") ? 0 : -1);
+    }();
+    return v;
 }
 
 static int dcn_backward_impl(DcnGeom& d, const float* weight, const float* gout, const float* gact, float gact_slope,
@@ -467,25 +476,22 @@ static int dcn_backward_impl(DcnGeom& d, const float* weight, const float* gout,
     TView g;
     g.p = gout; g.act = gact; g.slope = gact_slope; g.C = d.Co; g.Hs = g.Hv = d.Ho; g.Ws = g.Wv = d.Wo; g.mode = 0;
     const int nty = (d.Ho + 3) / 4;
-    // dcn_bwdin6 + dcn_bwdw6 run as a pair: the first leaves gOut (x act') behind as the matrix-core operands of the second
-    // developer A/B switch RVSR_DCN_BWD: 7 (default) = dcn_bwdin6 + dcn_bwdw6, 64 = dcn_bwdin6 + dcn_bwdw4, 6 = dcn_bwdin5 + dcn_bwdw4 (round 4's pair)
-    static const int gen_env = [] { const char* e = getenv("RVSR_DCN_BWD"); return e ? atoi(e) : 7; }();
-    static const int genw = gen_env == 7 ? 6 : 4;
+    const int pair = dcn_bwd_pair_switch();
+    if (pair < 0)
+        FAIL(RVSR_ERR_BAD_ARG, "dcn backward: RVSR_DCN_BWD=%.16s is not accepted: 7 (or unset) = dcn_bwdin6 + dcn_bwdw6, 64 = dcn_bwdin6 + dcn_bwdw4; "
+             "6 selected dcn_bwdin5, which was removed", getenv("RVSR_DCN_BWD"));
+    // ---- input / offset / mask gradient: dcn_bwdin6, else the first-generation kernel.  dcn_bwdin6 + dcn_bwdw6 run as a pair: the first leaves
+    // gOut (x act') behind as the matrix-core operands of the second, where the second will take the call
     void* agt = nullptr;
-    bool agt_written = false;
-    if (gx && gw && rvsr_gemm_mode_now() != 1 && genw >= 6 && dcn_bwd6_pair_possible(d.C, d.H, d.W, d.Co, d.stride, d.dil))
-        agt = (unsigned char*)workspace + dcn_backward_workspace_base(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil);
     if (gx || goff || gmask) {
         if (!gx || !goff || !gmask) FAIL(RVSR_ERR_BAD_ARG, "dcn backward: grad_input/grad_offset/grad_mask must be given together");
         int rc2 = RVSR_ERR_UNSUPPORTED;
         if (rvsr_gemm_mode_now() != 1) {
-            static const int gen = gen_env == 64 ? 7 : gen_env;
-            static const int halo = [] { const char* e = getenv("RVSR_DCN5_HALO"); return e ? atoi(e) : -1; }();   // -1: selected on the device
-            if (gen >= 7) {
-                rc2 = rvsr_launch_dcn_bwdin6(d, weight, g, gx, goff, goff_bs, gmask, gmask_bs, workspace, workspace_bytes, st, halo, probe, agt);
-                agt_written = rc2 == RVSR_OK && agt != nullptr;
-            }
-            if (rc2 == RVSR_ERR_UNSUPPORTED && gen >= 6) rc2 = rvsr_launch_dcn_bwdin5(d, weight, g, gx, goff, goff_bs, gmask, gmask_bs, workspace, workspace_bytes, st, halo, probe);
+            static const int halo = [] { const char* e = getenv("RVSR_DCN5_HALO"); return e ? atoi(e) : -1; }();   // dcn_bwdin6's window; -1: selected on the device
+            if (gw && pair == 1 && rvsr_dcn_bwdw6_takes(d) && dcn_bwd6_handoff_bytes(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil))
+                agt = (unsigned char*)workspace + dcn_backward_workspace_base(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil);
+            rc2 = rvsr_launch_dcn_bwdin6(d, weight, g, gx, goff, goff_bs, gmask, gmask_bs, workspace, workspace_bytes, st, halo, probe, agt);
+            if (rc2 != RVSR_OK) agt = nullptr;   // not written
         }
         if (rc2 != RVSR_ERR_UNSUPPORTED && rc2 != RVSR_OK) return rc2;
         DcnBwdInParams p;
@@ -495,7 +501,7 @@ static int dcn_backward_impl(DcnGeom& d, const float* weight, const float* gout,
         // (the LDS bound belongs to the first-generation kernel only: checked where that kernel is actually launched)
         if (rc2 != RVSR_OK && lds > 160 * 1024) FAIL(RVSR_ERR_UNSUPPORTED, "dcn backward: channels_out %d needs %zu B of LDS", d.Co, lds);
         if (rc2 == RVSR_OK) {
-            // done by dcn_bwdin6 / dcn_bwdin5
+            // done by dcn_bwdin6
         } else if (d.cpg % DCN_CC == 0) {
             if (set_lds(dcn_bwd_input_kernel<8>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_input: cannot reserve %zu B of LDS", lds);
             hipLaunchKernelGGL(dcn_bwd_input_kernel<8>, dim3(d.ntx * nty, 1, d.B), dim3(RVSR_WG), lds, st, p);
@@ -504,7 +510,8 @@ static int dcn_backward_impl(DcnGeom& d, const float* weight, const float* gout,
             hipLaunchKernelGGL(dcn_bwd_input_kernel<0>, dim3(d.ntx * nty, 1, d.B), dim3(RVSR_WG), lds, st, p);
         }
     }
-    if (gw && agt_written) {
+    // ---- weight / bias gradient: dcn_bwdw6 if the hand-off was written, else dcn_bwdw2 / dcn_bwdw4, else the first-generation kernel
+    if (gw && agt) {
         const int rc6 = rvsr_launch_dcn_bwdw6(d, agt, gw, gb, workspace, workspace_bytes, st);
         if (rc6 == RVSR_OK) gw = nullptr;   // done
         else if (rc6 != RVSR_ERR_UNSUPPORTED) return rc6;

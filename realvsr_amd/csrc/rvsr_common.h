@@ -149,7 +149,7 @@ __device__ __forceinline__ float tcat_get(const TCat& t, int bidx, int c, int y,
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side error plumbing (capi.hip)
+// host-side error plumbing (FAIL below; rvsr_last_error and the string itself: misc_kernels.hip)
 #define RVSR_OK 0
 #define RVSR_ERR_UNSUPPORTED 1
 #define RVSR_ERR_BAD_ARG 2

@@ -101,7 +101,7 @@ def test_dcn_pack_forward(speed_mode):
 
 
 def test_dcn_pack_backward(speed_mode):
-    """dcn_bwdin5 / dcn_bwdw4 in the speed modes against the three-term kernels on the same forward state (one seeded pack, 1.25 px
+    """dcn_bwdin6 / dcn_bwdw6 in the speed modes against the three-term kernels on the same forward state (one seeded pack, 1.25 px
     offsets): gradients of x, offsets + mask, weight and bias."""
     from realvsr_amd import _lib
     from realvsr_amd import functional as RF
@@ -240,7 +240,7 @@ def test_conv_shapes_in_the_speed_modes(case, speed_mode):
 
 def _speed_mode_dcn_cases():
     from test_gpu_dcn import SHAPES, _random_shapes
-    # more than 32 output channels, stride / dilation 1: dcn_fwd3<MT >= 2>, dcn_bwdin5<NK >= 4>, dcn_bwdw4 -- the kernels the modes act in
+    # more than 32 output channels, stride / dilation 1: dcn_fwd3<MT >= 2>, dcn_bwdin6<NK >= 4>, dcn_bwdw6 -- the kernels the modes act in
     return [c for c in SHAPES + _random_shapes(14, 928) if c[2] > 32 and c[6] == 1 and c[8] == 1]
 
 
