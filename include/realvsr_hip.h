@@ -49,14 +49,14 @@ const char* rvsr_last_error(void);
  * other operand hi + lo: exactly the result of mode 0 on bf16-rounded weights), 3 = one term (both
  * operands rounded to bf16); accumulation stays f32, ~2^-9 per product.  Modes 2 / 3 act in the
  * kernels that dominate a training step and ONLY there:
- *   conv_fwd5   3x3 stride-1 forward and data gradient, when C_out > 32 (64-row m-blocks) and
- *               the input view is one of the vector-staged ones (16-byte aligned, W % 4 == 0);
- *   conv_wgrad2 3x3 stride-1 weight gradient (W_out % 4 == 0, 16-byte aligned);
+ *   conv_fwd5   3x3 stride-1 forward and data gradient, where the plan (below) says 64-row m-blocks on a
+ *               vector-staged input view: rvsr_conv2d_forward_plan reports the term count of a call;
+ *   conv_wgrad2 / conv_wgrad5   the 3x3 stride-1 and the 5x5 weight gradient on the matrix cores;
  *   dcn_fwd3    fused DCN forward with C_out in {64, 128} (3x3, C % 8 == 0);
  *   dcn_bwdin6               fused DCN input / offset / mask gradient (3x3, stride 1, C % 8 == 0, C_out <= 128);
  *   dcn_bwdw4 / dcn_bwdw6    fused DCN weight gradient (same gate; bwdw4 also W_out % 4 == 0).
- * Every other kernel (1x1 and strided convs, narrow m-blocks such as the 3-channel output conv, scalar-staged views,
- * the generic DCN path of section 1c) computes three terms in modes 2 / 3, so a network off those shapes gets
+ * Every other kernel (1x1 and strided forward convs and their weight gradients, narrow m-blocks such as the 3-channel output conv,
+ * scalar-staged views, the generic DCN path of section 1c) computes three terms in modes 2 / 3, so a network off those shapes gets
  * mode 0's result and speed.  Other values select 0.  Process-wide switch. */
 void rvsr_set_gemm_mode(int mode);
 int rvsr_get_gemm_mode(void);   /* the mode the CALLING thread's next call computes in */
@@ -210,40 +210,53 @@ int rvsr_deform_conv_generic_backward(int dtype, const void* input, const void* 
  *   weight: w_mode 0 -> (Co, C1+C2, k, k) used as is;
  *           w_mode 1 -> (C1+C2, Co, k, k) used transposed + spatially flipped (data gradient);
  *           w_mode | 2: `workspace` already holds the packed image of these weights (section 2b), the per-call pack is skipped.
- *           w_mode | 4 (opt-in, with w_mode & 1 == 0, ksize 3, stride 1, Co1+Co2 > 32, in_mode 0, xact NULL, Ws % 4 == 0, 16-byte aligned
- *               inputs, a second input only behind a multiple of 16 channels; RVSR_ERR_UNSUPPORTED otherwise): this forward conv forms its
- *               products in the f16 + fp8 format -- a1*b1 on v_mfma_f32_32x32x16_f16 plus the cross terms a1*b2 + a2*b1 on
- *               v_mfma_scale_f32_32x32x64_f8f6f4 (a1 = f16(a), a2 = a - a1, fp8 e4m3 with the 2^12 in the block scales): 56 instead of
- *               108 matrix instructions per 16-channel stage, ~1.2e-5 instead of ~4.6e-6 relative l2 error per convolution (f32: 3e-7).
+ *           w_mode | 4 (opt-in): this forward conv forms its products in the f16 + fp8 format -- a1*b1 on v_mfma_f32_32x32x16_f16 plus
+ *               the cross terms a1*b2 + a2*b1 on v_mfma_scale_f32_32x32x64_f8f6f4 (a1 = f16(a), a2 = a - a1, fp8 e4m3 with the 2^12 in the
+ *               block scales): 56 instead of 108 matrix instructions per 16-channel stage, ~1.2e-5 instead of ~4.6e-6 relative l2 error
+ *               per convolution (f32: 3e-7).  Only the plain vector-staged conv_fwd5 kernels with 64-row m-blocks read such an image
+ *               (the rule: conv_fwd_plan, csrc/conv_plan.h); for any other call the flag is refused with RVSR_ERR_UNSUPPORTED and a
+ *               message, nothing is launched, and rvsr_conv2d_forward_plan gives the same answer beforehand.
  *               Activations must lie inside f16's range (|x| < 65504; below 6e-8 they round to zero).  A packed image (w_mode | 2) must
  *               have been written with the same flag.  realvsr_amd.set_gemm_mode('f16fp8') sets it on every eligible forward conv.
  *   out1 (B,Co1,Hout,Wout) [+ out2 (B,Co2,Hout,Wout): rows split, for the gradient of a cat].
  *   residual (NULL or shaped like out1, out2 must be NULL): added after the activation.
  *   act: 0 none, 1 ReLU, 2 LeakyReLU(slope); 3 (with `residual`, ksize 3, stride 1, one output): out = (conv + bias) * (residual > 0 ? 1 : slope),
  *        i.e. a data gradient multiplied by the derivative of the activation whose saved OUTPUT `residual` is -- the consumers of that
- *        gradient then need no mask.  Built for the 8 x 64-tile kernel only: returns RVSR_ERR_UNSUPPORTED (without an error message) for
- *        frames that kernel does not take, and the caller applies the mask on the consumer side (xact / gout_act) instead.
+ *        gradient then need no mask.  An epilogue of the 8 x 64-tile kernel only: for calls that kernel does not take the plan refuses
+ *        with RVSR_ERR_UNSUPPORTED and an empty message, nothing is launched, and the caller applies the mask on the consumer side
+ *        (xact / gout_act) instead.
  *   pixel_shuffle 1: out1 is (B,Co/4,2*Hout,2*Wout), written through PixelShuffle(2).
  *   stride 2 only with ksize 3 or 5 and in_mode 0.
- *   ksize 5 (pad 2; the patch discriminator, discriminator_arch.py:46-92): exact-f32 kernels in every GEMM mode (no packed image,
- *   workspace bytes 0, rvsr_conv2d_pack_weights returns 0); stride-2 data gradients through in_mode 1 as for 3x3.
- *   workspace: rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1+Co2, ksize) bytes (holds the weights
- *   re-packed as bf16 hi/lo for the matrix cores; unused in exact-f32 mode).
- *   Sizes: the fast kernels address one batch element of a tensor with 32-bit byte offsets (raw
- *   buffers); an input whose C*Hs*Ws*4 bytes reach 2 GB, or a concat whose first input is not a
- *   multiple of 16 channels, takes the scalar-staging / earlier-generation kernels (same results).
- *   3x3 stride-1 layers with Co <= 4 (conv_last) run on the vector ALU in exact f32 in both modes. */
+ *   ksize 5 (pad 2; the patch discriminator, discriminator_arch.py:46-92): stride-2 data gradients through in_mode 1 as for 3x3.
+ *   workspace: rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1+Co2, ksize) bytes (holds the weights re-packed as bf16 hi/lo for the
+ *   matrix cores; needed by the matrix-core kernels only).
+ *   Which kernel a call runs -- the vector-ALU kernel for <= 4 output channels, conv_fwd5 (3x3 stride 1) or conv_fwd2 (3x3 stride 2,
+ *   5x5, 1x1) on the bf16 matrix cores, or the exact-f32 kernel that takes everything else (GEMM mode 1, 5x5 through in_mode 1, inputs of
+ *   2 GB per batch element, a second input behind a channel count the chunked staging cannot split at) -- and its tile, staging view,
+ *   term count and grid are decided by ONE function, conv_fwd_plan (csrc/conv_plan.h), which states every rule once; all kernels
+ *   compute the same convolution. */
 size_t rvsr_conv2d_forward_workspace_bytes(int C1, int C2, int Co, int ksize);
 int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
                         int in_mode, int Hs, int Ws, const float* weight, const float* bias,
                         const float* residual, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
                         int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* That function's answer for a call, without running it (no GPU needed, nothing launched, no pointer dereferenced): the arguments of
+ * rvsr_conv2d_forward without workspace and stream; returns what the call itself would return before launching (RVSR_OK, a refusal or
+ * a bad-argument code, rvsr_last_error set alike) and fills plan[14] = {family (0 vector ALU, 1 conv_fwd5, 2 conv_fwd2, 3 exact f32;
+ * -1 refused), MT (32-row M tiles per workgroup), conv_fwd5's staging view (0 scalar, 1 plain, 2 pixel-unshuffle, 3 zero-insert),
+ * 8 x 64 tile, terms of a product (3, 2, 1; 4 = f16 + fp8), act' on the input, CCG / CC, 16-byte-store epilogue, tile h, tile w,
+ * grid x, y, z, LDS bytes}.  The host glue asks it where it has to know (realvsr_amd.functional: the w_mode | 4 gate, grad_mask_fusable). */
+int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
+                             int in_mode, int Hs, int Ws, const float* weight, const float* bias,
+                             const float* residual, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
+                             int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout, int* plan);
 
 /* 2b. Packed weight images, once per optimizer step.  The matrix-core kernels stage weights as bf16 hi/lo images
  *   ([m-block][chunk][hi|lo][tap][octet][row][8]); rvsr_conv2d_forward builds that image in its workspace on every call.
  *   rvsr_conv2d_pack_weights / rvsr_dcn_pack_weights write the image of one layer (forward: w_mode 0, data gradient: w_mode 1; w_mode 4:
- *   the forward image of a 3x3 layer with Co > 32 in the f16 + fp8 format of rvsr_conv2d_forward's w_mode | 4, for stride-1 use only) to
+ *   the forward image in the f16 + fp8 format of rvsr_conv2d_forward's w_mode | 4, for the layers that call grants it and for stride-1
+ *   use only, 0 otherwise) to
  *   caller-owned memory of rvsr_conv2d_forward_workspace_bytes(C_in, 0, Co, ksize) /
  *   rvsr_modulated_deform_conv_forward_workspace_bytes(channels, channels_out) bytes and return that size (0 = bad argument);
  *   `desc` (NULL or 10 x long long, host; 20 x long long for rvsr_dcn_pack_weights) receives {weight, out, Co, C_in, taps, MP, CCG,
@@ -262,7 +275,9 @@ int rvsr_pack_weights_batched(const void* descs, int n, void* stream);
  *         g_mode 2: stored (B,Co/4,Gs_h,Gs_w) pixel-shuffled (2*Hout, 2*Wout).
  *   gact/gact_slope: fused activation derivative (stored like gout), or NULL.
  *   accumulate 0: overwrite, 1: += .  Deterministic (fixed-order reduction of partials).
- *   ksize 5 (stride 1 or 2): exact-f32 kernel in every GEMM mode. */
+ *   Nine kernel families (vector ALU for <= 4 output channels; conv_wgrad2 / conv_wgrad5 / conv_wgrad1x1 / conv_wgrad_s2 on the bf16
+ *   matrix cores; an exact-f32 kernel per geometry, which also serves GEMM mode 1): conv_wgrad_plan (csrc/conv_plan.h) picks one and
+ *   its slicing into partial sums; the workspace query sizes for the largest slicing any family of the geometry can ask for. */
 size_t rvsr_conv2d_wgrad_workspace_bytes(int C1, int C2, int Co, int B, int ksize, int stride, int Hout, int Wout);
 int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
                                 const float* gout, const float* gact, float gact_slope, int g_mode,

@@ -16,6 +16,10 @@ _lib = None
 c_fp = ctypes.c_void_p  # device pointers travel as void*
 c_int, c_float, c_double, c_size = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
 
+# the convolution call itself: x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, ksize,
+# stride, w_mode, act, slope, pixel_shuffle, Hout, Wout
+_CONV_CALL = [c_fp, c_int, c_fp, c_int, c_fp, c_float, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int,
+              c_int, c_int, c_int, c_float, c_int, c_int, c_int]
 # name -> (restype, argtypes); must list every symbol declared in include/realvsr_hip.h
 SIGNATURES = {
     'rvsr_last_error': (ctypes.c_char_p, []),
@@ -34,9 +38,8 @@ SIGNATURES = {
     'rvsr_dcn_pack_forward': (c_int, [c_fp] * 5 + [c_int] * 10 + [c_float, c_fp, c_fp, c_size, c_fp]),
     'rvsr_dcn_offset_probe': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     'rvsr_dcn_pack_backward': (c_int, [c_fp] * 5 + [c_float] + [c_fp] * 4 + [c_int] * 9 + [c_fp, c_fp, c_size, c_fp]),
-    'rvsr_conv2d_forward': (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_float, c_int, c_int, c_int, c_fp, c_fp, c_fp,
-                                    c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
-                                    c_int, c_int, c_fp, c_size, c_fp]),
+    'rvsr_conv2d_forward': (c_int, _CONV_CALL + [c_fp, c_size, c_fp]),
+    'rvsr_conv2d_forward_plan': (c_int, _CONV_CALL + [ctypes.POINTER(c_int)]),
     'rvsr_conv2d_forward_workspace_bytes': (c_size, [c_int] * 4),
     'rvsr_conv2d_pack_weights': (c_size, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong), c_fp]),
     'rvsr_dcn_pack_weights': (c_size, [c_fp, c_int, c_int, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong), c_fp]),

@@ -15,7 +15,7 @@
 // MFMA operand maps (gfx950, 32x32x16): A[i = l&31][k = 8*(l>>5) + 0..7], B[k = 8*(l>>5) + 0..7][j = l&31],
 // D as in rvsr_common.h.
 #define RVSR_DEFINE_PACK
-#include "conv_common.h"
+#include "conv_plan.h"
 
 #include "bf16x3.h"
 
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
         if (VEC) {
             // Raw buffer addressing: weight image and the tile's batch element are buffer views, the (chunk, channel) part of an
             // address is a uniform byte offset in an SGPR, the per-lane part is the 32-bit it_sp (+ the lane's octet).  The
-            // staging carries no 64-bit per-lane address arithmetic and no validity selects (launch_fwd5 checks the 4 GB spans).
+            // staging carries no 64-bit per-lane address arithmetic and no validity selects (conv_fwd_plan, conv_plan.h, checks the spans).
             const unsigned wbase = (unsigned)(((size_t)t.mb * nchunks + chunk) * 2 * WVEC) * 16u;
 #pragma unroll
             for (int i = 0; i < NWV; ++i) {
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
         if (last_chunk) {  // last chunk of tile k: epilogue, fresh accumulators
             const Tile cur = tile_of(k);
             const float* bias_s = bias_base + (k & 3) * MP;
-            if (WIDE) {   // (launch_fwd5: 16-byte stores, no pixel shuffle, one output tensor)
+            if (WIDE) {   // (conv_fwd_plan: 16-byte stores, no pixel shuffle, one output tensor)
                 if (p.act == 3) conv2_epilogue_wide<MT, 4>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else if (p.res != nullptr) conv2_epilogue_wide<MT, 1>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else conv2_epilogue_wide<MT, 0>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
@@ -985,143 +985,72 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
 
 // ------------------------------------------------------------------------------------------
 // host side (called from conv_kernels.hip)
-// The f16 + fp8 product format (ConvFwdParams.fmt) exists in the 3x3 / stride-1 kernels with 64-row m-blocks, forward weights only
-static inline bool f16fp8_ok(int ksize, int stride, int mt, int w_mode) { return ksize == 3 && stride == 1 && mt == 2 && w_mode == 0; }
-static void fwd2_geom(int ksize, int Co, int Ctot, int& mt, int& ccg, int& nchunks, int& nmb) {
-    // never more than 2 M tiles per workgroup: the MT = 4 instantiation keeps 128 accumulator registers live and
-    // spills (130-190 VGPRs to scratch); two 64-row m-blocks re-stage the input tile but run spill-free
-    mt = (Co <= 32 || ksize == 5) ? 1 : 2;   // (5x5: 32-row m-blocks keep the 25-tap weight slice at 78 / 133 KB of LDS, stride 1 / 2)
-    ccg = ksize == 1 ? 2 : 1;
-    nchunks = (Ctot + 16 * ccg - 1) / (16 * ccg);
-    nmb = (Co + mt * 32 - 1) / (mt * 32);
-}
-
+// Which kernel, tile and grid: conv_plan.h.  Each launcher maps the plan's template coordinates to its kernel in one table.
 size_t rvsr_conv_fwd2_workspace_bytes(int ksize, int Co, int Ctot) {
     int mt, ccg, nchunks, nmb;
-    fwd2_geom(ksize, Co, Ctot, mt, ccg, nchunks, nmb);
+    conv_fwd2_geom(ksize, Co, Ctot, mt, ccg, nchunks, nmb);
     return (size_t)nmb * nchunks * 2 * (ksize * ksize) * (2 * ccg) * (mt * 32) * 16;
 }
 
-template <int KS, int STRIDE, int MT, int CCG>
-static int launch_fwd2(const ConvFwdParams& p, hipStream_t st) {
-    // 8 waves (16 rows x 32 px) per workgroup for the common stride-1 3x3 case: the weight slice is
-    // amortised over twice the pixels and 2 workgroups/CU = 16 waves hide the staging latency better
-    constexpr int NW = 4;  // (8 waves / 16x32 px measured 5% slower: 1.07 vs 1.00 ms on the 40x64x180x320 conv)
-    constexpr int T = KS * KS, IH = (2 * NW - 1) * STRIDE + KS, IW = 31 * STRIDE + KS;
-    const size_t lds = (size_t)16 * (2 * (2 * CCG) * IH * IW + 2 * T * (2 * CCG) * (MT * 32)) + sizeof(float) * MT * 32;
-    auto k = p.in.a.act != nullptr ? conv_fwd2_kernel<KS, STRIDE, MT, CCG, true, NW> : conv_fwd2_kernel<KS, STRIDE, MT, CCG, false, NW>;
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_fwd2: cannot reserve %zu B of LDS", lds);
-    const int nty = (p.Hout + 2 * NW - 1) / (2 * NW);
-    const long items = (long)p.ntx * nty * ((p.Co + MT * 32 - 1) / (MT * 32)) * p.B;
-    const int slots = 256 * (lds > 80 * 1024 ? 1 : 2);  // persistent: 2 workgroups per CU when LDS allows
-    dim3 grid((unsigned)(items < slots ? items : slots), 1, 1);
-    hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_fwd2 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+typedef void (*ConvFwdKernel)(const ConvFwdParams);
+
+// 4 waves (8 rows x 32 px) per workgroup  (8 waves / 16x32 px measured 5% slower: 1.07 vs 1.00 ms on the 40x64x180x320 conv)
+static ConvFwdKernel fwd2_kernel(int ksize, int stride, const ConvFwdPlan& q) {
+#define ROW(KS, STRIDE, MT, CCG) \
+    if (ksize == KS && stride == STRIDE && q.mt == MT) return q.act_in ? conv_fwd2_kernel<KS, STRIDE, MT, CCG, true, 4> : conv_fwd2_kernel<KS, STRIDE, MT, CCG, false, 4>
+    ROW(3, 2, 1, 1);
+    ROW(3, 2, 2, 1);
+    ROW(5, 1, 1, 1);
+    ROW(5, 2, 1, 1);
+    ROW(1, 1, 1, 2);
+    ROW(1, 1, 2, 2);
+#undef ROW
+    return nullptr;
 }
 
-template <int MT>
-static int launch_fwd5(const ConvFwdParams& p, hipStream_t st) {
-    constexpr int NX = 2 * 18 * 34, WVEC = 9 * 2 * MT * 32;
-    const size_t lds = (size_t)16 * (2 * 2 * NX + 2 * 2 * WVEC) + sizeof(float) * 4 * MT * 32 + 16;
-    const TView& va = p.in.a;
-    const TView& vb = p.in.b;
-    // VEC staging addresses one batch element of an input with 32-bit byte offsets (raw buffers) and selects the input per
-    // 16-channel chunk: planes of one element < 2 GB, a second input only behind a multiple of 16 channels
-    const size_t plane = sizeof(float) * (size_t)va.Hs * va.Ws;
-    const bool al16 = ((((uintptr_t)va.p) | ((uintptr_t)va.act) | ((uintptr_t)vb.p)) & 15) == 0;
-    int vec = 0;
-    if (va.mode == 0 && va.Ws % 4 == 0 && va.Wv == va.Ws && al16 &&
-        plane * (size_t)(va.C > vb.C ? va.C : vb.C) < ((size_t)1 << 31) && (vb.C == 0 || va.C % 16 == 0))
-        vec = 1;
-    else if (va.mode == 2 && vb.C == 0 && va.C % 16 == 0 && va.Wv % 4 == 0 && va.Ws == 2 * va.Wv && va.Hs == 2 * va.Hv && al16 &&
-             plane * (size_t)(va.C >> 2) < ((size_t)1 << 31))
-        vec = 2;
-    else if (va.mode == 1 && vb.C == 0 && va.Wv % 4 == 0 && va.Wv == 2 * va.Ws && va.Hv <= 2 * va.Hs && va.Ws % 2 == 0 && al16 &&
-             plane * (size_t)va.C < ((size_t)1 << 31))
-        vec = 3;
-    auto k = va.act != nullptr ? (vec == 3 ? conv_fwd5_kernel<MT, true, 3> : vec == 2 ? conv_fwd5_kernel<MT, true, 2>
-                                  : vec ? conv_fwd5_kernel<MT, true, 1> : conv_fwd5_kernel<MT, true, 0>)
-                               : (vec == 3 ? conv_fwd5_kernel<MT, false, 3> : vec == 2 ? conv_fwd5_kernel<MT, false, 2>
-                                  : vec ? conv_fwd5_kernel<MT, false, 1> : conv_fwd5_kernel<MT, false, 0>);
-    // reduced-term products (gemm modes 2 / 3): the 64-row m-block kernels on the vector-staged views; everything else keeps three terms
-    const int nt = (MT == 2 && vec != 0 && !p.fmt) ? rvsr_gemm_terms() : 3;
-    if constexpr (MT == 2) {
-#define FWD5_NT(NTV)                                                                                                                   \
-        k = va.act != nullptr ? (vec == 3 ? conv_fwd5_kernel<MT, true, 3, false, NTV> : vec == 2 ? conv_fwd5_kernel<MT, true, 2, false, NTV> \
-                                                                                      : conv_fwd5_kernel<MT, true, 1, false, NTV>)      \
-                              : (vec == 3 ? conv_fwd5_kernel<MT, false, 3, false, NTV> : vec == 2 ? conv_fwd5_kernel<MT, false, 2, false, NTV> \
-                                                                                       : conv_fwd5_kernel<MT, false, 1, false, NTV>)
-        if (nt == 2) { FWD5_NT(2); } else if (nt == 1) { FWD5_NT(1); }
-#undef FWD5_NT
-    }
-    if (p.fmt) {   // f16 + fp8 images: only the vector-staged kernels without act' read them
-        if constexpr (MT == 2) {
-            if (vec != 1 || va.act != nullptr) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: the f16 + fp8 format needs a plain 16-byte-aligned input view with W %% 4 == 0 and no act' tensor");
-            k = conv_fwd5_kernel<MT, false, 1, false, 4>;
-        } else {
-            FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: the f16 + fp8 format needs more than 32 output channels");
-        }
-    }
-    // tile shape: 8 x 64 (256-byte output runs, 16-byte stores, plain vector-staged view) when it wastes no more pixels than 16 x 32
-    int th = 16, tw = 32;
-    size_t lds_k = lds;
-    if (MT != 2 && p.act == 3) return RVSR_ERR_UNSUPPORTED;   // (mask epilogue: 8 x 64 tile, 64-row m-blocks only)
-    if constexpr (MT == 2) {
-        // (the 8 x 64 tile wherever it tiles the frame at least as well as 16 x 32)
-        const long px_n = (long)((p.Hout + 15) / 16 * 16) * ((p.Wout + 31) / 32 * 32), px_w = (long)((p.Hout + 7) / 8 * 8) * ((p.Wout + 63) / 64 * 64);
-        if (p.act == 3 && !(vec == 1 && p.vec4 && px_w <= px_n)) return RVSR_ERR_UNSUPPORTED;   // (mask epilogue: 8 x 64 tile only)
-        if (vec == 1 && p.vec4 && px_w <= px_n) {
-            k = va.act != nullptr ? conv_fwd5_kernel<MT, true, 1, true> : conv_fwd5_kernel<MT, false, 1, true>;
-            if (p.fmt) k = conv_fwd5_kernel<MT, false, 1, true, 4>;
-            if (nt == 2) k = va.act != nullptr ? conv_fwd5_kernel<MT, true, 1, true, 2> : conv_fwd5_kernel<MT, false, 1, true, 2>;
-            if (nt == 1) k = va.act != nullptr ? conv_fwd5_kernel<MT, true, 1, true, 1> : conv_fwd5_kernel<MT, false, 1, true, 1>;
-            th = 8; tw = 64;
-            constexpr int NXW = 2 * 10 * 66;
-            lds_k = (size_t)16 * (2 * 2 * NXW + 2 * 2 * WVEC) + sizeof(float) * 4 * MT * 32 + 16;
-        }
-    }
-    if (set_lds(k, lds_k)) FAIL(RVSR_ERR_LAUNCH, "conv_fwd5: cannot reserve %zu B of LDS", lds_k);
-    const int nty = (p.Hout + th - 1) / th;
-    const long items = (long)((p.Wout + tw - 1) / tw) * nty * ((p.Co + MT * 32 - 1) / (MT * 32)) * p.B;
-    dim3 grid((unsigned)(items < 256 ? items : 256), 1, 1);
-    hipLaunchKernelGGL(k, grid, dim3(512), lds_k, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_fwd5 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+static ConvFwdKernel fwd5_kernel(const ConvFwdPlan& q) {
+    // rows (MT, VEC, WIDE, NT), each with and without act' on the input (the f16 + fp8 images, NT 4: without only)
+#define ROW(MT, VEC, WIDE, NT) \
+    if (q.mt == MT && q.vec == VEC && q.wide == WIDE && q.nt == NT) return q.act_in ? conv_fwd5_kernel<MT, true, VEC, WIDE, NT> : conv_fwd5_kernel<MT, false, VEC, WIDE, NT>
+    ROW(2, 1, true, 3);    // the 8 x 64 tile
+    ROW(2, 1, true, 2);
+    ROW(2, 1, true, 1);
+    ROW(2, 1, false, 3);   // 16 x 32, 64-row m-blocks: the vector-staged views have the reduced-term variants
+    ROW(2, 1, false, 2);
+    ROW(2, 1, false, 1);
+    ROW(2, 2, false, 3);
+    ROW(2, 2, false, 2);
+    ROW(2, 2, false, 1);
+    ROW(2, 3, false, 3);
+    ROW(2, 3, false, 2);
+    ROW(2, 3, false, 1);
+    ROW(2, 0, false, 3);
+    ROW(1, 0, false, 3);   // 32-row m-blocks: three terms only
+    ROW(1, 1, false, 3);
+    ROW(1, 2, false, 3);
+    ROW(1, 3, false, 3);
+#undef ROW
+    if (q.mt == 2 && q.vec == 1 && q.nt == 4 && !q.act_in) return q.wide ? conv_fwd5_kernel<2, false, 1, true, 4> : conv_fwd5_kernel<2, false, 1, false, 4>;
+    return nullptr;
 }
 
-int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const int Ctot = p.in.a.C + p.in.b.C;
+int rvsr_launch_conv_fwd2(ConvFwdParams p, const ConvFwdPlan& q, int ksize, int stride, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const int Ctot = p.in.a.C + p.in.b.C, T = ksize * ksize;
     int mt, ccg, nchunks, nmb;
-    fwd2_geom(ksize, p.Co, Ctot, mt, ccg, nchunks, nmb);
+    conv_fwd2_geom(ksize, p.Co, Ctot, mt, ccg, nchunks, nmb);
     const size_t need = rvsr_conv_fwd2_workspace_bytes(ksize, p.Co, Ctot);
     if (!workspace || workspace_bytes < need) FAIL(RVSR_ERR_WORKSPACE, "conv2d: workspace %zu B < %zu B", workspace_bytes, need);
-    if (ksize == 5 && p.in.a.mode == 1) return RVSR_ERR_UNSUPPORTED;   // (conv_fwd2 stages plain and pixel-unshuffle views only)
-    if ((ksize != 3 || stride == 2) && p.in.a.mode == 0) {
-        // conv_fwd2_kernel stages a plain view through raw buffer loads: 32-bit byte offsets inside one batch element (< 2 GB),
-        // and a concat boundary on a chunk boundary; anything else goes back to the exact-f32 kernels of conv_kernels.hip
-        const size_t span = sizeof(float) * (size_t)p.in.a.Hs * p.in.a.Ws * (size_t)(p.in.a.C > p.in.b.C ? p.in.a.C : p.in.b.C);
-        if (span >= ((size_t)1 << 31) || (p.in.b.C != 0 && p.in.a.C % (16 * ccg) != 0)) return RVSR_ERR_UNSUPPORTED;
-    }
-    const int T = ksize * ksize;
-    const size_t total = (size_t)nmb * nchunks * T * (2 * ccg) * (mt * 32);
-    if (p.fmt && (!f16fp8_ok(ksize, stride, mt, p.w_mode) || rvsr_gemm_mode_now() == 1))
-        FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: the f16 + fp8 format (w_mode | 4) is for forward 3x3 / stride-1 convs with more than 32 output channels");
-    if (!p.prepacked)
+    const bool five = q.family == CONV_FWD5;
+    const ConvFwdKernel k = five ? fwd5_kernel(q) : fwd2_kernel(ksize, stride, q);
+    if (!k) FAIL(RVSR_ERR_LAUNCH, "conv2d: no %s instantiation for this plan", five ? "conv_fwd5" : "conv_fwd2");
+    if (!p.prepacked) {
+        const size_t total = (size_t)nmb * nchunks * T * (2 * ccg) * (mt * 32);
         hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.w, (bf16x8*)workspace, p.Co,
                            Ctot, T, mt * 32, ccg, nchunks, nmb, p.w_mode | (p.fmt ? 0x100 : 0));
+    }
     p.wpack = workspace;
-    p.swz = rvsr_swizzle_enabled();
-    // (the 16-byte-store epilogues address one batch element of the output / residual with 32-bit byte offsets in a 2 GB buffer view)
-    p.vec4 = (p.Wout % 4 == 0) && ((((uintptr_t)p.out1) | ((uintptr_t)p.res)) & 15) == 0 && !p.ps && p.out2 == nullptr &&
-             sizeof(float) * (size_t)p.Co * p.Hout * p.Wout < ((size_t)1 << 31);
-    // (mt is 1 or 2: fwd2_geom)
-    if (ksize == 3 && stride == 1) return mt == 1 ? launch_fwd5<1>(p, st) : launch_fwd5<2>(p, st);
-    if (ksize == 3 && stride == 2) return mt == 1 ? launch_fwd2<3, 2, 1, 1>(p, st) : launch_fwd2<3, 2, 2, 1>(p, st);
-    if (ksize == 5) return stride == 1 ? launch_fwd2<5, 1, 1, 1>(p, st) : launch_fwd2<5, 2, 1, 1>(p, st);
-    return mt == 1 ? launch_fwd2<1, 1, 1, 2>(p, st) : launch_fwd2<1, 1, 2, 2>(p, st);
+    p.vec4 = q.vec4;
+    return rvsr_conv_launch(five ? "conv_fwd5" : "conv_fwd2", k, dim3(q.gx), five ? 512 : 256, q.lds, st, p);
 }
 
 // Pre-packed weight images (include/realvsr_hip.h section 2b): the image rvsr_conv2d_forward would build in its workspace,
@@ -1131,10 +1060,10 @@ extern "C" size_t rvsr_conv2d_pack_weights(const float* weight, int C_in, int Co
                                            long long* desc, void* stream) {
     int mt, ccg, nchunks, nmb;
     if (ksize != 1 && ksize != 3 && ksize != 5) return 0;
-    fwd2_geom(ksize, Co, C_in, mt, ccg, nchunks, nmb);
+    conv_fwd2_geom(ksize, Co, C_in, mt, ccg, nchunks, nmb);
     const size_t need = rvsr_conv_fwd2_workspace_bytes(ksize, Co, C_in);
     if (!weight || !out || out_bytes < need) return 0;
-    if ((w_mode & 4) && !f16fp8_ok(ksize, 1, mt, w_mode & 1)) return 0;   // (the caller vouches for stride 1)
+    if ((w_mode & 4) && !conv_f16fp8_ok(ksize, 1, mt, w_mode & 1)) return 0;   // (the caller vouches for stride 1)
     const int fmtflag = (w_mode & 4) ? 0x100 : 0;
     const int T = ksize * ksize;
     const size_t total = (size_t)nmb * nchunks * T * (2 * ccg) * (mt * 32);
@@ -1529,21 +1458,23 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
     }
 }
 
+typedef void (*ConvWgradKernel)(const ConvWgradParams);
+
 int rvsr_launch_conv_wgrad2(const ConvWgradParams& p, int gy, int gz, hipStream_t st) {
     const size_t lds = 2 * 64 * WG2_GP + 2 * 64 * WG2_XP + 64 * sizeof(float);
     const bool act = p.g.act != nullptr;
-    auto k = p.g.mode == 0 ? (act ? conv_wgrad2_kernel<true, 0> : conv_wgrad2_kernel<false, 0>)
-                           : (act ? conv_wgrad2_kernel<true, 2> : conv_wgrad2_kernel<false, 2>);
     const int nt = rvsr_gemm_terms();   // reduced-term products (gemm modes 2 / 3)
-    if (nt == 2) k = p.g.mode == 0 ? (act ? conv_wgrad2_kernel<true, 0, 2> : conv_wgrad2_kernel<false, 0, 2>)
-                                   : (act ? conv_wgrad2_kernel<true, 2, 2> : conv_wgrad2_kernel<false, 2, 2>);
-    if (nt == 1) k = p.g.mode == 0 ? (act ? conv_wgrad2_kernel<true, 0, 1> : conv_wgrad2_kernel<false, 0, 1>)
-                                   : (act ? conv_wgrad2_kernel<true, 2, 1> : conv_wgrad2_kernel<false, 2, 1>);
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad2: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(k, dim3(p.P, gy, gz), dim3(WG2_THREADS), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad2 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    ConvWgradKernel k = nullptr;
+#define ROW(GMODE, NT) \
+    if (p.g.mode == GMODE && nt == NT) k = act ? conv_wgrad2_kernel<true, GMODE, NT> : conv_wgrad2_kernel<false, GMODE, NT>
+    ROW(0, 3);
+    ROW(0, 2);
+    ROW(0, 1);
+    ROW(2, 3);
+    ROW(2, 2);
+    ROW(2, 1);
+#undef ROW
+    return rvsr_conv_launch("conv_wgrad2", k, dim3(p.P, gy, gz), WG2_THREADS, lds, st, p);
 }
 
 // ==========================================================================================
@@ -1637,10 +1568,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad1x1_kernel(const ConvWgradPa
 
 int rvsr_launch_conv_wgrad1x1(const ConvWgradParams& p, int gy, int gz, hipStream_t st) {
     auto k = p.g.act != nullptr ? conv_wgrad1x1_kernel<true> : conv_wgrad1x1_kernel<false>;
-    hipLaunchKernelGGL(k, dim3(p.P, gy, gz), dim3(256), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad1x1 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    return rvsr_conv_launch("conv_wgrad1x1", k, dim3(p.P, gy, gz), 256, 0, st, p);
 }
 
 // ==========================================================================================
@@ -1748,10 +1676,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2_kernel(const ConvWgradPa
 
 int rvsr_launch_conv_wgrad_s2(const ConvWgradParams& p, int gy, int gz, hipStream_t st) {
     auto k = p.g.act != nullptr ? conv_wgrad_s2_kernel<true> : conv_wgrad_s2_kernel<false>;
-    hipLaunchKernelGGL(k, dim3(p.P, gy, gz), dim3(256), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad_s2 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    return rvsr_conv_launch("conv_wgrad_s2", k, dim3(p.P, gy, gz), 256, 0, st, p);
 }
 
 // ==========================================================================================
@@ -1849,24 +1774,19 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad5_kernel(const ConvWgradPara
     }
 }
 
-int rvsr_conv_wgrad5_P(int B, int Hout, int Wout, int Co, int Ctot) {
-    const long ntiles = (long)B * ((Hout + 3) / 4) * ((Wout + 31) / 32);
-    long P = 256 / ((long)((Co + 31) / 32) * ((Ctot + 31) / 32));
-    if (P < 1) P = 1;
-    if (P > ntiles) P = ntiles;
-    return (int)P;
-}
-
-int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, hipStream_t st) {
-    const int Ctot = p.x.a.C + p.x.b.C;
+int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, int gy, int gz, hipStream_t st) {
     const int IH = 3 * stride + 5, IW = 31 * stride + 5;
     const size_t lds = sizeof(float) * (32 * (4 * 32 + 1) + 32 * ((IH * IW) | 1));
     const int nt = rvsr_gemm_terms();
-    auto k = stride == 1 ? (nt == 1 ? conv_wgrad5_kernel<1, 1> : nt == 2 ? conv_wgrad5_kernel<1, 2> : conv_wgrad5_kernel<1, 3>)
-                         : (nt == 1 ? conv_wgrad5_kernel<2, 1> : nt == 2 ? conv_wgrad5_kernel<2, 2> : conv_wgrad5_kernel<2, 3>);
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad5: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(k, dim3(p.P, (p.Co + 31) / 32, (Ctot + 31) / 32), dim3(256), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad5 launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    ConvWgradKernel k = nullptr;
+#define ROW(STRIDE, NT) \
+    if (stride == STRIDE && nt == NT) k = conv_wgrad5_kernel<STRIDE, NT>
+    ROW(1, 3);
+    ROW(1, 2);
+    ROW(1, 1);
+    ROW(2, 3);
+    ROW(2, 2);
+    ROW(2, 1);
+#undef ROW
+    return rvsr_conv_launch("conv_wgrad5", k, dim3(p.P, gy, gz), 256, lds, st, p);
 }

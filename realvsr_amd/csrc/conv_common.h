@@ -84,18 +84,24 @@ struct ConvWgradParams {
 };
 
 
-// bf16x3 path (conv2_kernels.hip)
+// Launchers.  Which of them a call reaches, and with what grid, is decided in conv_plan.h; they map the plan to a kernel and launch it.
+struct ConvFwdPlan;
+// one launch of a planned kernel: opt into its dynamic LDS, launch, report
+template <typename K, typename P>
+static inline int rvsr_conv_launch(const char* name, K k, dim3 grid, unsigned threads, size_t lds, hipStream_t st, const P& p) {
+    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "%s: cannot reserve %zu B of LDS", name, lds);
+    hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "%s launch: %s", name, hipGetErrorString(e));
+    return RVSR_OK;
+}
+// bf16x3 path (conv2_kernels.hip): conv_fwd5 / conv_fwd2 behind their packed weight image (built in `workspace` unless p.prepacked)
 size_t rvsr_conv_fwd2_workspace_bytes(int ksize, int Co, int Ctot);
-int rvsr_launch_conv_fwd2(ConvFwdParams p, int ksize, int stride, void* workspace, size_t workspace_bytes, hipStream_t st);
-
+int rvsr_launch_conv_fwd2(ConvFwdParams p, const ConvFwdPlan& q, int ksize, int stride, void* workspace, size_t workspace_bytes, hipStream_t st);
 int rvsr_launch_conv_wgrad2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad1x1(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad_s2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
-// 5x5 (stride 1 / 2) weight gradient on the bf16 matrix cores: one partial per workgroup of its own grid (P from rvsr_conv_wgrad5_P)
-int rvsr_conv_wgrad5_P(int B, int Hout, int Wout, int Co, int Ctot);
-int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, hipStream_t st);
+int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, int gy, int gz, hipStream_t st);
 // conv_thin_kernels.hip: 3x3 / stride-1 layers with <= 4 output channels on the vector ALU (exact f32)
-int rvsr_conv_wgrad_thin_P(int B, int Hout, int Wout);
 int rvsr_launch_conv_wgrad_thin(const ConvWgradParams& p, hipStream_t st);
-bool rvsr_conv_fwd_thin_ok(const ConvFwdParams& p, int ksize, int stride);
-int rvsr_launch_conv_fwd_thin(const ConvFwdParams& p, hipStream_t st);
+int rvsr_launch_conv_fwd_thin(const ConvFwdParams& p, const ConvFwdPlan& q, hipStream_t st);

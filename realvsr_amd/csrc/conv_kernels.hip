@@ -19,7 +19,7 @@
 // buffer exists anywhere.
 #include "rvsr_common.h"
 
-#include "conv_common.h"
+#include "conv_plan.h"
 
 template <int KS, int STRIDE, int MT, int CC>
 __global__ __launch_bounds__(RVSR_WG, 2) void conv_fwd_kernel(const ConvFwdParams p) {
@@ -261,18 +261,19 @@ __global__ __launch_bounds__(RVSR_WG) void conv_wgrad_kernel(const ConvWgradPara
 // host side
 
 
-template <int KS, int STRIDE, int MT, int CC>
-static int launch_fwd(const ConvFwdParams& p, hipStream_t st) {
-    constexpr int T = KS * KS, IH = 7 * STRIDE + KS, IW = 31 * STRIDE + KS;
-    const size_t lds = sizeof(float) * (CC * IH * IW + T * CC * (MT * 32 + 1));
-    auto k = conv_fwd_kernel<KS, STRIDE, MT, CC>;
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_fwd: cannot reserve %zu B of LDS", lds);
-    const int nty = (p.Hout + 7) / 8;
-    dim3 grid(p.ntx * nty, (p.Co + MT * 32 - 1) / (MT * 32), p.B);
-    hipLaunchKernelGGL(k, grid, dim3(RVSR_WG), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_fwd launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+// exact-f32 forward: the plan's (MT, CC) per geometry
+static int launch_fwd(const ConvFwdParams& p, const ConvFwdPlan& q, int ksize, int stride, hipStream_t st) {
+    void (*k)(const ConvFwdParams) = nullptr;
+#define ROW(KS, STRIDE, CC12, CC4)                                                 \
+    if (ksize == KS && stride == STRIDE)                                           \
+        k = q.mt == 1 ? conv_fwd_kernel<KS, STRIDE, 1, CC12> : q.mt == 2 ? conv_fwd_kernel<KS, STRIDE, 2, CC12> : conv_fwd_kernel<KS, STRIDE, 4, CC4>
+    ROW(3, 1, 16, 8);
+    ROW(3, 2, 8, 4);
+    ROW(5, 1, 8, 4);
+    ROW(5, 2, 4, 4);
+    ROW(1, 1, 32, 32);
+#undef ROW
+    return rvsr_conv_launch("conv_fwd", k, dim3(q.gx, q.gy, q.gz), RVSR_WG, q.lds, st, p);
 }
 
 static int make_view(TView& v, const float* p, const float* act, float slope, int C, int Hs, int Ws, int mode,
@@ -300,13 +301,11 @@ static int make_view(TView& v, const float* p, const float* act, float slope, in
     return 0;
 }
 
-// Fused conv block.  See include/realvsr_hip.h for the contract.
-extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const float* xact,
-                                   float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
-                                   const float* bias, const float* residual, float* out1, int Co1, float* out2,
-                                   int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
-                                   int pixel_shuffle, int Hout, int Wout, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
+// Validates a rvsr_conv2d_forward call and fills its parameter block (wpack and vec4: rvsr_launch_conv_fwd2, from the plan).
+static int conv_fwd_params(ConvFwdParams& p, const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
+                           int in_mode, int Hs, int Ws, const float* weight, const float* bias, const float* residual, float* out1,
+                           int Co1, float* out2, int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                           int pixel_shuffle, int Hout, int Wout) {
     if (!x1 || !weight || !out1 || B <= 0 || C1 <= 0 || Co1 <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d: null/empty argument");
     if ((x2 == nullptr) != (C2 == 0) || (out2 == nullptr) != (Co2 == 0))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: second input/output pointer and channel count disagree");
@@ -316,7 +315,6 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     if (xact && x2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: act' fusion with concat input");
     if ((residual || pixel_shuffle) && out2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual/pixel-shuffle with split output");
     if (residual && pixel_shuffle) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual with pixel-shuffle");
-    ConvFwdParams p;
     if (make_view(p.in.a, x1, xact, xact_slope, C1, Hs, Ws, in_mode, Hout, Wout))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: bad input view (mode %d, C %d, %dx%d)", in_mode, C1, Hs, Ws);
     make_view(p.in.b, x2, nullptr, 0.f, C2, Hs, Ws, 0, 0, 0);
@@ -324,6 +322,9 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     const int He = (p.in.a.Hv + 2 * pad - ksize) / stride + 1, We = (p.in.a.Wv + 2 * pad - ksize) / stride + 1;
     if (He != Hout || We != Wout) FAIL(RVSR_ERR_BAD_ARG, "conv2d: output size %dx%d, expected %dx%d", Hout, Wout, He, We);
     p.w = weight;
+    p.wpack = nullptr;
+    p.swz = rvsr_swizzle_enabled();
+    p.vec4 = 0;
     p.bias = bias;
     p.res = residual;
     p.out1 = out1;
@@ -341,35 +342,48 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     p.slope = slope;
     p.ps = pixel_shuffle;
     p.ntx = (Wout + 31) / 32;
+    return RVSR_OK;
+}
+// A refusal of the plan: nothing is launched.  (No message for act 3 -- the caller has a plan B -- and no stale one either.)
+static int conv_fwd_refuse(const ConvFwdPlan& q) {
+    snprintf(rvsr_g_err, sizeof(rvsr_g_err), "%s", q.msg ? q.msg : "");
+    return q.rc;
+}
+
+// Fused conv block.  See include/realvsr_hip.h for the contract: validate, plan (conv_plan.h), refuse or launch.
+extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                   float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                   const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                                   int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                   int pixel_shuffle, int Hout, int Wout, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    ConvFwdParams p;
+    const int rc = conv_fwd_params(p, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B,
+                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout);
+    if (rc) return rc;
+    const ConvFwdPlan q = conv_fwd_plan(p, ksize, stride, rvsr_gemm_mode_now());
+    if (q.rc) return conv_fwd_refuse(q);
     hipStream_t st = (hipStream_t)stream;
-    p.wpack = nullptr;
-    if (act == 3) {
-        // out = (conv + bias) * (residual > 0 ? 1 : slope): the data gradient of a layer whose INPUT was an activation output, with that
-        // activation's derivative applied on the way out (`residual` = the saved activation output).  Only the 8 x 64-tile kernel has this
-        // epilogue; everything else answers "unsupported" and the caller applies the mask on the consumer side as before.
-        if (!residual || ksize != 3 || stride != 1 || pixel_shuffle || out2 || rvsr_gemm_mode_now() == 1) return RVSR_ERR_UNSUPPORTED;
-        return rvsr_launch_conv_fwd2(p, ksize, stride, workspace, workspace_bytes, st);
+    switch (q.family) {
+        case CONV_FWD_THIN: return rvsr_launch_conv_fwd_thin(p, q, st);
+        case CONV_FWD_F32: return launch_fwd(p, q, ksize, stride, st);
+        default: return rvsr_launch_conv_fwd2(p, q, ksize, stride, workspace, workspace_bytes, st);   // conv_fwd5 / conv_fwd2
     }
-    if (rvsr_conv_fwd_thin_ok(p, ksize, stride)) return rvsr_launch_conv_fwd_thin(p, st);   // <= 4 output channels: vector ALU, exact f32
-    // 5x5 (the patch discriminator, archs/discriminator_arch.py): conv_fwd2 at KS = 5 except through the zero-insert view of a stride-2
-    // data gradient (in_mode 1), which only the 3x3 kernels stage: that one takes the exact-f32 kernels below
-    if (rvsr_gemm_mode_now() != 1 && (in_mode != 1 || ksize == 3) && (x2 == nullptr || C1 % 8 == 0)) {
-        const int rc2 = rvsr_launch_conv_fwd2(p, ksize, stride, workspace, workspace_bytes, st);
-        if (rc2 != RVSR_ERR_UNSUPPORTED) return rc2;   // (sizes beyond the buffer-addressed kernels: exact-f32 kernels below)
-    }
-    const int mt = p.Co <= 32 ? 1 : (p.Co <= 64 ? 2 : 4);
-#define DISPATCH(KS, S, CC12, CC4)                                \
-    do {                                                           \
-        if (mt == 1) return launch_fwd<KS, S, 1, CC12>(p, st);     \
-        if (mt == 2) return launch_fwd<KS, S, 2, CC12>(p, st);     \
-        return launch_fwd<KS, S, 4, CC4>(p, st);                   \
-    } while (0)
-    if (ksize == 3 && stride == 1) DISPATCH(3, 1, 16, 8);
-    if (ksize == 3 && stride == 2) DISPATCH(3, 2, 8, 4);
-    if (ksize == 5 && stride == 1) DISPATCH(5, 1, 8, 4);     // LDS: 66 / 58 KB (2 workgroups per CU)
-    if (ksize == 5) DISPATCH(5, 2, 4, 4);                    // 34 / 46 / 72 KB
-    DISPATCH(1, 1, 32, 32);
-#undef DISPATCH
+}
+// The plan of that call, without a GPU: same arguments, same return code (and rvsr_last_error), nothing launched.
+extern "C" int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                        float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                        const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                                        int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                        int pixel_shuffle, int Hout, int Wout, int* plan) {
+    ConvFwdParams p;
+    const int rc = conv_fwd_params(p, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B,
+                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout);
+    if (rc) return rc;
+    const ConvFwdPlan q = conv_fwd_plan(p, ksize, stride, rvsr_gemm_mode_now());
+    const int row[14] = {q.family, q.mt, q.vec, q.wide, q.nt, q.act_in, q.cc, q.vec4, q.th, q.tw, (int)q.gx, (int)q.gy, (int)q.gz, (int)q.lds};
+    for (int i = 0; plan && i < 14; ++i) plan[i] = row[i];
+    return q.rc ? conv_fwd_refuse(q) : RVSR_OK;
 }
 
 int rvsr_g_gemm_mode = 0;                  // process-wide default
@@ -381,59 +395,16 @@ extern "C" size_t rvsr_conv2d_forward_workspace_bytes(int C1, int C2, int Co, in
     return rvsr_conv_fwd2_workspace_bytes(ksize, Co, C1 + C2);
 }
 
-static int wgrad_P(int ntiles, int gy, int gz, int ksize) {
-    // 1x1: the GEMM kernel runs 4 small workgroups per CU and hides its load latency with occupancy
-    int P = (ksize == 1 ? 1024 : 256) / (gy * gz);
-    if (P < 1) P = 1;
-    if (P > ntiles) P = ntiles;
-    return P;
-}
-// stride-2 bf16x3 kernel: 2 workgroups of 4 waves per CU, pixels cut into 16-pixel units
-static int wgrad_s2_P(int B, int Hout, int Wout, int gy, int gz64) {
-    long units = (long)B * Hout * ((Wout + 15) / 16);
-    int P = 512 / (gy * gz64);
-    if (P < 1) P = 1;
-    if (P > units) P = (int)units;
-    return P;
-}
-static void wgrad_geom(int ksize, int stride, int Co, int Ctot, int& ccw, int& gy, int& gz) {
-    // 5x5: 16 input channels per workgroup = 400 GEMM columns, 7 accumulator tiles per wave (64 would need 25)
-    ccw = ksize == 5 ? 16 : ((ksize == 3 && stride == 2) ? 32 : 64);
-    gy = (Co + 63) / 64;
-    gz = (Ctot + ccw - 1) / ccw;
-}
-
 extern "C" size_t rvsr_conv2d_wgrad_workspace_bytes(int C1, int C2, int Co, int B, int ksize, int stride, int Hout,
                                                     int Wout) {
-    int ccw, gy, gz;
-    wgrad_geom(ksize, stride, Co, C1 + C2, ccw, gy, gz);
-    const int ntiles = B * ((Hout + 3) / 4) * ((Wout + 31) / 32);
-    size_t P = wgrad_P(ntiles, gy, gz, ksize);
-    if (ksize == 3 && stride == 2) {  // the bf16x3 stride-2 kernel slices the pixels differently
-        const size_t P2 = wgrad_s2_P(B, Hout, Wout, gy, (C1 + C2 + 63) / 64);
-        if (P2 > P) P = P2;
-    }
-    if (ksize == 5) {   // so does the bf16x3 5x5 kernel
-        const size_t P5 = rvsr_conv_wgrad5_P(B, Hout, Wout, Co, C1 + C2);
-        if (P5 > P) P = P5;
-    }
-    if (ksize == 3 && stride == 1 && Co <= 4) {  // the thin-layer kernel keeps one partial per workgroup of its own grid
-        const size_t P3 = rvsr_conv_wgrad_thin_P(B, Hout, Wout);
-        if (P3 > P) P = P3;
-    }
+    const size_t P = conv_wgrad_max_P(ksize, stride, B, Hout, Wout, Co, C1 + C2);
     return sizeof(float) * P * ((size_t)Co * (C1 + C2) * ksize * ksize + Co);
 }
 
 template <int KS, int STRIDE, int CCW>
 static int launch_wgrad(const ConvWgradParams& p, int gy, int gz, hipStream_t st) {
     constexpr int IH = 3 * STRIDE + KS, IW = 31 * STRIDE + KS, CS = (IH * IW) | 1;
-    const size_t lds = sizeof(float) * (128 * 65 + CCW * CS);
-    auto k = conv_wgrad_kernel<KS, STRIDE, CCW>;
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(k, dim3(p.P, gy, gz), dim3(RVSR_WG), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    return rvsr_conv_launch("conv_wgrad", conv_wgrad_kernel<KS, STRIDE, CCW>, dim3(p.P, gy, gz), RVSR_WG, sizeof(float) * (128 * 65 + CCW * CS), st, p);
 }
 
 extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
@@ -458,60 +429,31 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
     const int pad = ksize / 2;
     if ((Hin + 2 * pad - ksize) / stride + 1 != Hout || (Win + 2 * pad - ksize) / stride + 1 != Wout)
         FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: input %dx%d does not give output %dx%d", Hin, Win, Hout, Wout);
-    int ccw, gy, gz;
-    const int Ctot = C1 + C2;
-    wgrad_geom(ksize, stride, Co, Ctot, ccw, gy, gz);
     p.B = B;
     p.Co = Co;
     p.Hout = Hout;
     p.Wout = Wout;
     p.ntx = (Wout + 31) / 32;
     p.nty = (Hout + 3) / 4;
-    p.P = wgrad_P(B * p.nty * p.ntx, gy, gz, ksize);
     p.ring = 0;   // (the X-row ring of conv_wgrad2 measured no gain, profiles/r04_notes.md: compiled out, WGRAD2_RING in conv2_kernels.hip)
-    const size_t nw = (size_t)Co * Ctot * ksize * ksize;
+    const ConvWgradPlan q = conv_wgrad_plan(p, ksize, stride, rvsr_gemm_mode_now());
+    const size_t nw = (size_t)Co * (C1 + C2) * ksize * ksize;
+    p.P = q.P;
     p.part = (float*)workspace;
     p.bpart = grad_bias ? p.part + (size_t)p.P * nw : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    const bool aligned16 = ((((uintptr_t)x1) | ((uintptr_t)x2) | ((uintptr_t)gout) | ((uintptr_t)gact)) & 15) == 0;
-    if (ksize == 3 && stride == 1 && Co <= 4 && C2 == 0 && C1 % 16 == 0 && g_mode == 0 && (Wout % 4) == 0 && aligned16 &&
-        sizeof(float) * (size_t)Hout * Wout * (size_t)C1 < ((size_t)1 << 31)) {
-        // thin layer (conv_last): vector-ALU kernel, exact f32 in both GEMM modes
-        p.P = rvsr_conv_wgrad_thin_P(B, Hout, Wout);
-        p.bpart = grad_bias ? p.part + (size_t)p.P * nw : nullptr;
-        rc = rvsr_launch_conv_wgrad_thin(p, st);
-        if (rc) return rc;
-        rvsr_launch_reduce(p.part, p.P, nw, grad_weight, accumulate, st, p.bpart, (size_t)Co, grad_bias);
-        hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad reduce launch: %s", hipGetErrorString(e2));
-        return RVSR_OK;
+    int rc = RVSR_ERR_UNSUPPORTED;
+    switch (q.family) {
+        case CONV_WGRAD_THIN: rc = rvsr_launch_conv_wgrad_thin(p, st); break;
+        case CONV_WGRAD2: rc = rvsr_launch_conv_wgrad2(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD5: rc = rvsr_launch_conv_wgrad5(p, stride, q.gy, q.gz, st); break;
+        case CONV_WGRAD_F32_5: rc = stride == 1 ? launch_wgrad<5, 1, 16>(p, q.gy, q.gz, st) : launch_wgrad<5, 2, 16>(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_1X1: rc = rvsr_launch_conv_wgrad1x1(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_F32_3S1: rc = launch_wgrad<3, 1, 64>(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_S2: rc = rvsr_launch_conv_wgrad_s2(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_F32_3S2: rc = launch_wgrad<3, 2, 32>(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_F32_1: rc = launch_wgrad<1, 1, 64>(p, q.gy, q.gz, st); break;
     }
-    // conv_wgrad2 addresses one image of each tensor with 32-bit byte offsets (raw buffers, < 2 GB) and picks the input per
-    // 64-channel block: a second input has to start on a multiple of 64 channels
-    const size_t img_max = sizeof(float) * (size_t)Hout * Wout * (size_t)(Co > Ctot ? Co : Ctot);
-    if (rvsr_gemm_mode_now() != 1 && ksize == 3 && stride == 1 && (Wout % 4) == 0 && aligned16 && img_max < ((size_t)1 << 31) &&
-        (C2 == 0 || C1 % 64 == 0))
-        rc = rvsr_launch_conv_wgrad2(p, gy, gz, st);
-    else if (ksize == 5 && rvsr_gemm_mode_now() != 1) {   // bf16 matrix cores (the mode's terms), deterministic partials like the others
-        p.P = rvsr_conv_wgrad5_P(B, Hout, Wout, Co, Ctot);
-        p.bpart = grad_bias ? p.part + (size_t)p.P * nw : nullptr;
-        rc = rvsr_launch_conv_wgrad5(p, stride, st);
-    } else if (ksize == 5)   // exact-f32 mode
-        rc = stride == 1 ? launch_wgrad<5, 1, 16>(p, gy, gz, st) : launch_wgrad<5, 2, 16>(p, gy, gz, st);
-    else if (rvsr_gemm_mode_now() != 1 && ksize == 1 && g_mode == 0 && ((Hout * Wout) % 8) == 0 && aligned16)
-        rc = rvsr_launch_conv_wgrad1x1(p, gy, gz, st);
-    else if (ksize == 3 && stride == 1)
-        rc = launch_wgrad<3, 1, 64>(p, gy, gz, st);
-    else if (ksize == 3 && rvsr_gemm_mode_now() != 1 && x2 == nullptr && g_mode == 0 && (Wout % 8) == 0 && (Win % 4) == 0 && aligned16) {
-        const int gz64 = (Ctot + 63) / 64;
-        p.P = wgrad_s2_P(B, Hout, Wout, gy, gz64);
-        p.bpart = grad_bias ? p.part + (size_t)p.P * nw : nullptr;
-        rc = rvsr_launch_conv_wgrad_s2(p, gy, gz64, st);
-    } else if (ksize == 3)
-        rc = launch_wgrad<3, 2, 32>(p, gy, gz, st);
-    else
-        rc = launch_wgrad<1, 1, 64>(p, gy, gz, st);
     if (rc) return rc;
     rvsr_launch_reduce(p.part, p.P, nw, grad_weight, accumulate, st, p.bpart, (size_t)Co, grad_bias);
     hipError_t e = hipGetLastError();

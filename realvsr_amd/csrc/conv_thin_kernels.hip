@@ -8,7 +8,7 @@
 // range-check zero padding (see conv_fwd5_kernel), deterministic partial sums reduced by rvsr_reduce_partials_kernel.
 // Measured: 0.84 ms per call at 8 x 64 x 720 x 1280 (conv_wgrad2: 1.45 ms); 30 TFLOP/s, issue-bound (288 packed FMAs + ~300
 // other instructions per thread and tile, two barriers per tile).
-#include "conv_common.h"
+#include "conv_plan.h"
 
 #define THIN_T 256           // threads per workgroup
 #define THIN_XW 72           // staged columns of a row: image columns x0-4 .. x0+67
@@ -147,17 +147,9 @@ __global__ __launch_bounds__(THIN_T, 3) void conv_wgrad_thin_kernel(const ConvWg
     }
 }
 
-int rvsr_conv_wgrad_thin_P(int B, int Hout, int Wout) {
-    const long ntiles = (long)B * ((Hout + 3) / 4) * ((Wout + 63) / 64);
-    return (int)(ntiles < 768 ? ntiles : 768);   // 3 workgroups of 4 waves per CU
-}
-
 int rvsr_launch_conv_wgrad_thin(const ConvWgradParams& p, hipStream_t st) {
     auto k = p.g.act != nullptr ? conv_wgrad_thin_kernel<true> : conv_wgrad_thin_kernel<false>;
-    hipLaunchKernelGGL(k, dim3(p.P), dim3(THIN_T), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_wgrad_thin launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+    return rvsr_conv_launch("conv_wgrad_thin", k, dim3(p.P), THIN_T, 0, st, p);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -166,8 +158,7 @@ int rvsr_launch_conv_wgrad_thin(const ConvWgradParams& p, hipStream_t st) {
 // 64 channels) against ~0.4 ms of HBM time.  Here one workgroup computes an 8 x 128 pixel tile, a thread four consecutive pixels
 // of one row for all output channels; the input passes through LDS as f32 eight channels at a time, the weights sit in LDS as
 // [c][tap][o0..o3] so that one broadcast 16-byte read feeds two packed FMAs per pixel.
-#define THIN_FW 136          // staged columns per row: image columns x0-4 .. x0+131
-#define THIN_FPL (10 * THIN_FW)
+// (THIN_FW = 136 staged columns per row, THIN_FPL: conv_plan.h, which sizes the LDS)
 __global__ __launch_bounds__(THIN_T, 2) void conv_fwd_thin_kernel(const ConvFwdParams p) {
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     float* const xs = fsm;                    // [8 ch][10 rows][136 cols]
@@ -264,20 +255,6 @@ __global__ __launch_bounds__(THIN_T, 2) void conv_fwd_thin_kernel(const ConvFwdP
     }
 }
 
-// 3x3 / stride 1 / plain view / single input and output / no act' / f32 weights in the reference layout
-bool rvsr_conv_fwd_thin_ok(const ConvFwdParams& p, int ksize, int stride) {
-    const TView& va = p.in.a;
-    return ksize == 3 && stride == 1 && p.Co <= 4 && p.in.b.C == 0 && va.C % 8 == 0 && va.mode == 0 && va.act == nullptr &&
-           p.out2 == nullptr && !p.ps && p.w_mode == 0 && p.Wout % 4 == 0 && va.Ws == p.Wout && va.Hs == p.Hout &&
-           ((((uintptr_t)va.p) | ((uintptr_t)p.out1) | ((uintptr_t)p.res)) & 15) == 0 &&
-           sizeof(float) * (size_t)p.Hout * p.Wout * (size_t)va.C < ((size_t)1 << 31) && va.C <= 256;
-}
-int rvsr_launch_conv_fwd_thin(const ConvFwdParams& p, hipStream_t st) {
-    const size_t lds = sizeof(float) * (8 * THIN_FPL + (size_t)p.in.a.C * 36);
-    if (set_lds(conv_fwd_thin_kernel, lds)) FAIL(RVSR_ERR_LAUNCH, "conv_fwd_thin: cannot reserve %zu B of LDS", lds);
-    const unsigned grid = (unsigned)p.B * ((p.Hout + 7) / 8) * ((p.Wout + 127) / 128);
-    hipLaunchKernelGGL(conv_fwd_thin_kernel, dim3(grid), dim3(THIN_T), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "conv_fwd_thin launch: %s", hipGetErrorString(e));
-    return RVSR_OK;
+int rvsr_launch_conv_fwd_thin(const ConvFwdParams& p, const ConvFwdPlan& q, hipStream_t st) {
+    return rvsr_conv_launch("conv_fwd_thin", conv_fwd_thin_kernel, dim3(q.gx), THIN_T, q.lds, st, p);
 }

@@ -143,18 +143,19 @@ def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode
     w_mode = 1 if transposed else 0
     L = _lib.lib()
     nbytes = L.rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1 + Co2, k)
-    if (_lib.fmt_f16fp8() and k == 3 and stride == 1 and w_mode == 0 and Co1 + Co2 > 32 and xact is None and in_mode == 0 and Ws % 4 == 0
-            and (C2 == 0 or C1 % 16 == 0) and (x1.data_ptr() | (0 if x2 is None else x2.data_ptr())) % 16 == 0):
-        w_mode |= 4     # 'f16fp8' mode: this forward conv in the f16 + fp8 product format (weight image and kernel; _lib.set_gemm_mode)
+    call = (_p(x1), C1, _p(x2), C2, _p(xact), xact_slope, in_mode, Hs, Ws, _p(weight), _p(bias), _p(residual), _p(out1), Co1, _p(out2), Co2,
+            B, k, stride)
+    tail = (act, slope, int(pixel_shuffle), Hout, Wout)
+    # 'f16fp8' mode (_lib.set_gemm_mode): every forward conv the library's plan grants the f16 + fp8 product format (weight image and kernel)
+    if _lib.fmt_f16fp8() and L.rvsr_conv2d_forward_plan(*call, w_mode | 4, *tail, None) == 0:
+        w_mode |= 4
     # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused)
     buf = None if k == 5 and in_mode == 1 else packed_weights.get(weight, 'conv', C1 + C2, Co1 + Co2, k, w_mode, nbytes)
     if buf is not None:
         ws, w_mode = buf, w_mode | 2
     else:
         ws = _workspace(nbytes, torch.device('cuda', torch.cuda.current_device()))
-    rc = L.rvsr_conv2d_forward(_p(x1), C1, _p(x2), C2, _p(xact), xact_slope, in_mode, Hs, Ws, _p(weight), _p(bias), _p(residual),
-                               _p(out1), Co1, _p(out2), Co2, B, k, stride, w_mode, act, slope, int(pixel_shuffle), Hout, Wout,
-                               _p(ws), ws.numel(), _stream())
+    rc = L.rvsr_conv2d_forward(*call, w_mode, *tail, _p(ws), ws.numel(), _stream())
     if rc == 1 and act == ACT_MASK:     # RVSR_ERR_UNSUPPORTED: the fused gradient mask is an option of one kernel, the caller has a plan B
         return False
     _lib.check(rc, what)
@@ -433,12 +434,20 @@ def conv2d(x, conv, act=ACT_NONE, slope=0.1, x2=None, residual=None, pixel_shuff
                               grad_premasked)
 
 
+_mask_fusable = {}   # (H, W, GEMM mode) -> the plan's answer
+
+
 def grad_mask_fusable(H, W):
-    """Whether the data-gradient kernel of a 3x3 stride-1 conv on H x W frames has the mask epilogue (the 8 x 64 tile: chosen when it
-    wastes no more pixels than 16 x 32, conv2_kernels.hip launch_fwd5).  Where it has not, x_premask costs a separate pass."""
-    px_n = ((H + 15) // 16 * 16) * ((W + 31) // 32 * 32)
-    px_w = ((H + 7) // 8 * 8) * ((W + 63) // 64 * 64)
-    return _FUSE_GRAD_MASK and W % 4 == 0 and px_w <= px_n
+    """Whether the data-gradient kernel of a 3x3 stride-1 conv on H x W frames has the mask epilogue (act 3 of rvsr_conv2d_forward): the
+    library's plan is asked about the call this stands for, 64 -> 64 channels on aligned tensors.  Where it has not, x_premask costs a
+    separate pass."""
+    L = _lib.lib()
+    key = (H, W, L.rvsr_get_gemm_mode())
+    if key not in _mask_fusable:
+        a = _lib.c_fp(1 << 20)   # any 16-byte-aligned address: the plan reads none
+        _mask_fusable[key] = L.rvsr_conv2d_forward_plan(a, 64, None, 0, None, 0.0, 0, H, W, a, None, a, a, 64, None, 0, 1, 3, 1, 1,
+                                                        ACT_MASK, 0.1, 0, H, W, None) == 0
+    return _FUSE_GRAD_MASK and _mask_fusable[key]
 
 
 # ------------------------------------------------------------------------------------------ DCN

@@ -146,3 +146,61 @@ def test_conv_wgrad_is_deterministic():
         RF.conv2d(x, conv, RF.ACT_LRELU).square().sum().backward()
         grads.append(conv.weight.grad.clone())
     assert torch.equal(grads[0], grads[1])
+
+
+# ---- refusals of the plan (csrc/conv_plan.h), straight through the C ABI: nothing may be launched
+SENTINEL = -12345.0
+
+
+def _raw_conv(x, w, bias, res, out, w_mode, act, slope=0.1):
+    """rvsr_conv2d_forward on a single-input 3x3 / stride-1 conv; returns (code, message)."""
+    from realvsr_amd import _lib
+    from realvsr_amd._lib import _p, _stream
+    L = _lib.lib()
+    B, C, H, W = x.shape
+    Co = out.shape[1]
+    ws = torch.empty(L.rvsr_conv2d_forward_workspace_bytes(C, 0, Co, 3), dtype=torch.uint8, device=x.device)
+    rc = L.rvsr_conv2d_forward(_p(x), C, None, 0, None, 0.0, 0, H, W, _p(w), _p(bias), _p(res), _p(out), Co, None, 0, B, 3, 1, w_mode, act,
+                               slope, 0, H, W, _p(ws), ws.numel(), _stream())
+    torch.cuda.synchronize()
+    return rc, (L.rvsr_last_error() or b'').decode()
+
+
+@pytest.fixture
+def bf16x3_mode():
+    from realvsr_amd import _lib
+    old = _lib.get_gemm_mode()
+    _lib.set_gemm_mode('bf16x3')
+    yield
+    _lib.set_gemm_mode(old)
+
+
+def test_f16fp8_flag_on_an_ineligible_conv_is_refused(bf16x3_mode):
+    """w_mode | 4 on a conv with 32 output channels: RVSR_ERR_UNSUPPORTED with a message that names the format, and no kernel runs
+    (before the plan the call fell through to the exact-f32 kernel and returned RVSR_OK)."""
+    d = dev()
+    g = torch.Generator().manual_seed(5)
+    x, w, b = (torch.randn(s, generator=g).to(d) for s in ((1, 16, 8, 8), (32, 16, 3, 3), (32,)))
+    out = torch.full((1, 32, 8, 8), SENTINEL, device=d)
+    rc, msg = _raw_conv(x, w, b, None, out, 4, 0)
+    assert rc == 1 and 'f16 + fp8' in msg, (rc, msg)
+    assert bool((out == SENTINEL).all())
+
+
+def test_mask_epilogue_refused_or_exact(bf16x3_mode):
+    """act 3 (out = (conv + bias) * (residual > 0 ? 1 : slope)): refused without a message and without touching the output on a frame the
+    8 x 64 tile does not take (16 x 24); computed on one it takes (8 x 64)."""
+    d = dev()
+    g = torch.Generator().manual_seed(6)
+    w, b = torch.randn(64, 64, 3, 3, generator=g) / 72.0, torch.randn(64, generator=g) * 0.1
+    for H, W, taken in ((16, 24, False), (8, 64, True)):
+        x, res = torch.randn(1, 64, H, W, generator=g), torch.randn(1, 64, H, W, generator=g)
+        out = torch.full((1, 64, H, W), SENTINEL, device=d)
+        rc, msg = _raw_conv(x.to(d), w.to(d), b.to(d), res.to(d), out, 0, 3, 0.1)
+        if not taken:
+            assert rc == 1 and msg == '', (rc, msg)
+            assert bool((out == SENTINEL).all())
+        else:
+            assert rc == 0, (rc, msg)
+            ref = F.conv2d(x.double(), w.double(), b.double(), padding=1) * torch.where(res.double() > 0, 1.0, 0.1)
+            check('masked data gradient', out, ref, TOLS['bf16x3'])

@@ -457,3 +457,152 @@ def test_packed_weights_validity_rules_on_cpu():
         assert pw.get(w, *geo) is None and not pw.entries
         f1, f2 = pw.split(w, 1), pw.split(w, 1)
         assert f1[0] is not f2[0] and torch.equal(f1[0], f2[0]) and not pw.slices
+
+
+# ---- the conv plan (csrc/conv_plan.h) through its exported query: no GPU, made-up addresses
+_A = 0x10000000   # 16-byte aligned; the plan dereferences nothing
+
+
+def _conv_plan(C1=64, Co=64, H=45, W=80, *, B=2, C2=0, xact=False, in_mode=0, k=3, stride=1, w_mode=0, act=0, residual=False, Co2=0,
+               x_off=0, out_off=0, Hout=None, Wout=None, gemm=None):
+    """(rc, message, plan row) of rvsr_conv2d_forward_plan for a conv of (B, C1 [+ C2], H, W) stored input."""
+    import ctypes
+    from realvsr_amd import _lib
+    L = _lib.lib()
+    pad = k // 2
+    if Hout is None:
+        Hv, Wv = (H // 2, W // 2) if in_mode == 2 else (H, W)
+        Hout, Wout = (Hv + 2 * pad - k) // stride + 1, (Wv + 2 * pad - k) // stride + 1
+    p = lambda off, on=True: ctypes.c_void_p(_A + off) if on else None   # noqa: E731
+    row = (ctypes.c_int * 14)(*([-7] * 14))
+    L.rvsr_set_gemm_mode_thread(-1 if gemm is None else gemm)
+    try:
+        rc = L.rvsr_conv2d_forward_plan(p(0x100000 + x_off), C1, p(0x200000, C2), C2, p(0x300000, xact), 0.1, in_mode, H, W, p(0x400000),
+                                        p(0x500000), p(0x600000, residual), p(0x700000 + out_off), Co, p(0x800000, Co2), Co2, B, k, stride,
+                                        w_mode, act, 0.1, 0, Hout, Wout, row)
+    finally:
+        L.rvsr_set_gemm_mode_thread(-1)
+    return rc, L.rvsr_last_error().decode(), dict(zip(('family', 'MT', 'vec', 'wide', 'NT', 'act_in', 'CC', 'vec4', 'th', 'tw', 'gx', 'gy',
+                                                       'gz', 'lds'), row))
+
+
+THIN, FWD5, FWD2, F32 = 0, 1, 2, 3
+# Expected rows, worked out by hand from the dispatcher this plan replaced (the entry of conv_kernels.hip, rvsr_launch_conv_fwd2 and
+# launch_fwd5 / launch_fwd2 of conv2_kernels.hip before the plan existed), B = 2, 64 -> 64 channels, 45 x 80 unless stated.
+_PLAN_ROWS = [
+    # 3x3 stride 1: conv_fwd5
+    (dict(H=180, W=320), dict(family=FWD5, MT=2, vec=1, wide=1, NT=3, act_in=0, CC=1, vec4=1, th=8, tw=64, gx=230, gy=1, gz=1, lds=159248)),
+    (dict(), dict(family=FWD5, MT=2, vec=1, wide=0, NT=3, act_in=0, CC=1, vec4=1, th=16, tw=32, gx=18, gy=1, gz=1, lds=153104)),
+    (dict(W=30), dict(family=FWD5, MT=2, vec=0, wide=0, NT=3, vec4=0, th=16, tw=32, gx=6, lds=153104)),
+    (dict(H=180, W=320, x_off=4, out_off=4), dict(family=FWD5, MT=2, vec=0, wide=0, NT=3, vec4=0, gx=240)),
+    (dict(H=180, W=320, x_off=4), dict(family=FWD5, vec=0, wide=0, vec4=1)),
+    (dict(H=180, W=320, out_off=4), dict(family=FWD5, vec=1, wide=0, vec4=0)),
+    (dict(H=180, W=320, xact=True), dict(family=FWD5, MT=2, vec=1, wide=1, NT=3, act_in=1)),
+    (dict(C1=64, H=90, W=160, in_mode=2), dict(family=FWD5, MT=2, vec=2, wide=0, NT=3, vec4=1, gx=18)),
+    (dict(H=23, W=40, in_mode=1, Hout=45, Wout=80, w_mode=1), dict(family=FWD5, MT=2, vec=3, wide=0, NT=3, vec4=1, gx=18)),
+    (dict(Co=3), dict(family=THIN, MT=1, NT=3, vec4=0, th=8, tw=128, gx=12, gy=1, gz=1, lds=52736)),
+    (dict(Co=3, xact=True), dict(family=FWD5, MT=1, vec=1, act_in=1)),          # (the vector-ALU kernel has no act' load)
+    (dict(Co=32), dict(family=FWD5, MT=1, vec=1, wide=0, NT=3, vec4=1, th=16, tw=32, gx=18, lds=115728)),
+    (dict(Co=32, H=180, W=320), dict(family=FWD5, MT=1, vec=1, wide=0)),        # (the 8 x 64 tile: 64-row m-blocks only)
+    (dict(C2=64), dict(family=FWD5, MT=2, vec=1, wide=0, NT=3)),
+    (dict(C1=24, C2=16), dict(family=FWD5, MT=2, vec=0, wide=0, NT=3)),         # a second input behind 8 k channels: scalar staging
+    (dict(C1=20, C2=16), dict(family=F32, MT=2, CC=16, th=8, tw=32, gx=18, gy=1, gz=2, lds=59200)),
+    (dict(C2=64, Co=32, Co2=32), dict(family=FWD5, MT=2, vec=1, vec4=0, wide=0)),   # split output: element stores
+    # 1x1, 3x3 stride 2, 5x5: conv_fwd2, or exact f32 where its chunked staging cannot split the concat
+    (dict(k=1, C1=32, C2=32), dict(family=FWD2, MT=2, CC=2, NT=3, th=8, tw=32, gx=36, gy=1, gz=1, lds=41216)),
+    (dict(k=1, C1=16, C2=16), dict(family=F32, MT=2, CC=32, gx=18, gy=1, gz=2, lds=41088)),
+    (dict(k=3, C1=24, C2=16, stride=2), dict(family=F32, MT=2, CC=8)),
+    (dict(stride=2), dict(family=FWD2, MT=2, CC=1, NT=3, act_in=0, vec4=1, gx=12, lds=107840)),
+    (dict(stride=2, xact=True), dict(family=FWD2, act_in=1)),
+    (dict(k=5), dict(family=FWD2, MT=1, CC=1, NT=3, gx=72, lds=78976)),
+    (dict(k=5, stride=2), dict(family=FWD2, MT=1, CC=1, NT=3, gx=24, lds=132800)),
+    (dict(k=5, H=23, W=40, in_mode=1, Hout=45, Wout=80, w_mode=1), dict(family=F32, MT=2, CC=8, gx=18, gy=1, gz=2, lds=65824)),
+    (dict(k=5, Co=216), dict(family=FWD2, MT=1)),
+    # GEMM mode 1: exact f32 everywhere but the vector-ALU kernel; modes 2 / 3: fewer terms in conv_fwd5 with 64-row m-blocks on a
+    # vector-staged view, three terms everywhere else
+    (dict(H=180, W=320, gemm=1), dict(family=F32, MT=2, CC=16, NT=3, gx=230, gy=1, gz=2, lds=59200)),
+    (dict(Co=216, gemm=1), dict(family=F32, MT=4, CC=8, gy=2)),
+    (dict(Co=3, gemm=1), dict(family=THIN)),
+    (dict(H=180, W=320, gemm=2), dict(family=FWD5, MT=2, vec=1, wide=1, NT=2)),
+    (dict(H=180, W=320, gemm=3), dict(family=FWD5, MT=2, vec=1, wide=1, NT=1)),
+    (dict(gemm=2), dict(family=FWD5, MT=2, vec=1, wide=0, NT=2)),
+    (dict(C1=64, H=90, W=160, in_mode=2, gemm=3), dict(family=FWD5, vec=2, NT=1)),
+    (dict(H=23, W=40, in_mode=1, Hout=45, Wout=80, w_mode=1, gemm=2), dict(family=FWD5, vec=3, NT=2)),
+    (dict(Co=32, gemm=2), dict(family=FWD5, MT=1, vec=1, NT=3)),
+    (dict(W=30, gemm=3), dict(family=FWD5, MT=2, vec=0, NT=3)),
+    (dict(stride=2, gemm=2), dict(family=FWD2, NT=3)),
+    (dict(k=1, gemm=3), dict(family=FWD2, NT=3)),
+    # the f16 + fp8 format and the mask epilogue where they exist
+    (dict(H=180, W=320, w_mode=4), dict(family=FWD5, MT=2, vec=1, wide=1, NT=4, act_in=0, lds=159248)),
+    (dict(w_mode=4, gemm=2), dict(family=FWD5, MT=2, vec=1, wide=0, NT=4)),
+    (dict(w_mode=6, C2=64), dict(family=FWD5, vec=1, NT=4)),
+    (dict(H=8, W=64, act=3, residual=True, w_mode=1), dict(family=FWD5, MT=2, vec=1, wide=1, NT=3, th=8, tw=64, gx=2)),
+    (dict(H=8, W=64, act=3, residual=True, w_mode=1, xact=True, gemm=3), dict(family=FWD5, wide=1, NT=1, act_in=1)),
+]
+_FMT = 'f16 + fp8'
+_REFUSALS = [   # (call, the message names this)
+    (dict(w_mode=4, Co=32), _FMT), (dict(w_mode=4, xact=True), _FMT), (dict(w_mode=4, W=30), _FMT), (dict(w_mode=4, gemm=1), _FMT),
+    (dict(w_mode=5), _FMT), (dict(w_mode=4, stride=2), _FMT), (dict(w_mode=4, k=1), _FMT), (dict(w_mode=4, Co=3), _FMT),
+    (dict(w_mode=4, C1=24, C2=16), _FMT), (dict(w_mode=4, x_off=4), _FMT), (dict(w_mode=4, Co=32, act=3, residual=True), _FMT),
+    (dict(act=3, residual=True, H=16, W=24), ''), (dict(act=3, residual=True, H=8, W=64, Co=32), ''),
+    (dict(act=3, residual=True, H=8, W=64, gemm=1), ''), (dict(act=3, H=8, W=64), ''), (dict(act=3, residual=True, H=8, W=64, out_off=4), ''),
+    (dict(act=3, residual=True, H=8, W=62), ''), (dict(act=3, residual=True, H=16, W=128, stride=2), ''),
+]
+
+
+def test_conv_forward_plan_rows():
+    """Which kernel, tile and grid a rvsr_conv2d_forward call gets: one row per family and per coordinate that can differ."""
+    for call, want in _PLAN_ROWS:
+        rc, _, row = _conv_plan(**call)
+        assert rc == 0, call
+        got = {key: row[key] for key in want}
+        assert got == want, (call, row)
+    # after a per-thread mode the thread is back on the process-wide one
+    assert _conv_plan(H=180, W=320)[2]['NT'] == 3
+
+
+def test_conv_forward_plan_refusals():
+    """A refusal is RVSR_ERR_UNSUPPORTED with a message that names the format, or -- act 3, where the caller has a plan B -- with none;
+    bad arguments keep their own code."""
+    assert _conv_plan()[0] == 0
+    for call, text in _REFUSALS:
+        rc, msg, row = _conv_plan(**call)
+        assert rc == 1 and row['family'] == -1, (call, rc, row)
+        assert (text in msg) if text else msg == '', (call, msg)
+    rc, msg, row = _conv_plan(Hout=44, Wout=80)
+    assert rc == 2 and 'output size' in msg and row['family'] == -7      # (a call that is not valid has no plan: the row is untouched)
+
+
+def test_grad_mask_fusable_asks_the_plan():
+    from realvsr_amd import functional as RF
+    for hw in ((180, 320), (720, 1280), (8, 64)):
+        assert RF.grad_mask_fusable(*hw) is True, hw
+    for hw in ((45, 80), (90, 160), (16, 24), (64, 96), (8, 62)):
+        assert RF.grad_mask_fusable(*hw) is False, hw
+    old = RF._FUSE_GRAD_MASK
+    try:
+        RF._FUSE_GRAD_MASK = False
+        assert RF.grad_mask_fusable(180, 320) is False
+    finally:
+        RF._FUSE_GRAD_MASK = old
+
+
+def test_conv_workspace_bytes_pinned():
+    """rvsr_conv2d_forward_workspace_bytes / rvsr_conv2d_wgrad_workspace_bytes: values of the library before the weight-gradient plan
+    (the query takes the largest slicing among the families that can take the geometry)."""
+    from realvsr_amd import _lib
+    L = _lib.lib()
+    pins = {   # (C1, C2, Co, B, ksize, stride, Hout, Wout): (forward bytes, weight-gradient bytes)
+        (64, 0, 64, 40, 3, 1, 180, 320): (147456, 37814272),
+        (64, 0, 3, 8, 3, 1, 180, 320): (73728, 5317632),
+        (64, 64, 64, 8, 3, 1, 45, 80): (294912, 37781504),
+        (64, 0, 64, 8, 3, 2, 45, 80): (147456, 75628544),
+        (3, 0, 64, 8, 5, 2, 45, 80): (102400, 4980736),
+        (320, 0, 64, 8, 1, 1, 45, 80): (81920, 16763904),
+        (16, 0, 33, 1, 5, 1, 7, 9): (102400, 105864),
+        (128, 0, 216, 1, 3, 2, 16, 24): (1179648, 31878144),
+        (64, 0, 4, 1, 3, 1, 7, 9): (73728, 18464),
+    }
+    for (C1, C2, Co, B, k, s, H, W), want in pins.items():
+        got = (L.rvsr_conv2d_forward_workspace_bytes(C1, C2, Co, k), L.rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, k, s, H, W))
+        assert got == want, (C1, C2, Co, B, k, s, H, W, got)
