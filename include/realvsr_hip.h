@@ -52,9 +52,10 @@ const char* rvsr_last_error(void);
  *   conv_fwd5   3x3 stride-1 forward and data gradient, where the plan (below) says 64-row m-blocks on a
  *               vector-staged input view: rvsr_conv2d_forward_plan reports the term count of a call;
  *   conv_wgrad2 / conv_wgrad5   the 3x3 stride-1 and the 5x5 weight gradient on the matrix cores;
- *   dcn_fwd3    fused DCN forward with C_out in {64, 128} (3x3, C % 8 == 0);
- *   dcn_bwdin6               fused DCN input / offset / mask gradient (3x3, stride 1, C % 8 == 0, C_out <= 128);
- *   dcn_bwdw4 / dcn_bwdw6    fused DCN weight gradient (same gate; bwdw4 also W_out % 4 == 0).
+ *   dcn_fwd3    fused DCN forward with C_out > 32;
+ *   dcn_bwdin6               fused DCN input / offset / mask gradient with C_out > 32;
+ *   dcn_bwdw4 / dcn_bwdw6    fused DCN weight gradient
+ *   (which DCN calls these kernels take: dcn_fwd_plan / dcn_bwd_plan, csrc/dcn_plan.h; rvsr_dcn_pack_*_plan report the term count of a call).
  * Every other kernel (1x1 and strided forward convs and their weight gradients, narrow m-blocks such as the 3-channel output conv,
  * scalar-staged views, the generic DCN path of section 1c) computes three terms in modes 2 / 3, so a network off those shapes gets
  * mode 0's result and speed.  Other values select 0.  Process-wide switch. */
@@ -77,7 +78,15 @@ void rvsr_set_gemm_mode_thread(int mode);
  * The reference's `ones` / `columns` temporaries do not exist here (the column tile lives in LDS).
  * HIP path: kh = kw = 3, group = 1, isotropic stride/pad/dilation, C/dg dividing or a multiple of 8.
  * workspace: rvsr_modulated_deform_conv_forward_workspace_bytes(channels, channels_out) bytes for
- * the bf16 hi/lo re-packed weights of the bf16x3 kernel; NULL selects the exact-f32 kernel. */
+ * the bf16 hi/lo re-packed weights of the bf16x3 kernels; NULL selects the exact-f32 kernel.
+ * Which kernels a DCN call runs -- forward: dcn_fwd3 (stride 1, dilation 1; tile halo 3 / 7 / 11 px, selected on the device among up to
+ * three launches, or fixed by the caller's hint), dcn_fwd2 (other strides / dilations, frames beyond 4 GB per batch element) or the
+ * exact-f32 dcn_fwd_kernel (GEMM mode 1, no workspace, fewer than 8 channels per deformable group); backward: dcn_bwdin6 + dcn_bwdw6 as
+ * a pair, dcn_bwdw4 / dcn_bwdw2 for a weight gradient alone or a view the pair does not take, the first-generation kernels for the
+ * rest -- with their tiles, term counts, candidates, grids, whether the probe pass and the weight pack run, and the layout of the
+ * backward's workspace, is decided by dcn_fwd_plan / dcn_bwd_plan / dcn_bwd_workspace (csrc/dcn_plan.h), which state every rule once.
+ * Entries validate, plan, refuse or launch in order; a refused call (RVSR_ERR_WORKSPACE included) launches nothing, the probe pass
+ * included.  All kernels of a direction compute the same function. */
 size_t rvsr_modulated_deform_conv_forward_workspace_bytes(int channels, int channels_out);
 int rvsr_modulated_deform_conv_forward(const float* input, const float* weight, const float* bias,
                                        const float* offset, const float* mask, float* output,
@@ -165,6 +174,33 @@ int rvsr_dcn_pack_backward(const float* input, const float* weight, const float*
                            float* grad_bias, float* grad_om, int batch, int channels, int height, int width,
                            int channels_out, int stride, int pad, int dilation, int deformable_group,
                            const void* probe, void* workspace, size_t workspace_bytes, void* stream);
+/* The plans of these two calls, without running them (no GPU needed, nothing launched, no pointer dereferenced): the arguments of the
+ * call without the stream; return what the call itself would return before launching (rvsr_last_error set alike) and fill
+ *   forward  plan[36] = {family (0 dcn_fwd3, 1 dcn_fwd2<8, MT>, 2 dcn_fwd_kernel<MT, CHS>; -1 refused), MT, CHS, terms of a product,
+ *            weight pack runs, probe pass runs, its samples, launches (1-3), 3 x {halo, ge, lt, ge2, thr_ge, thr_lt, thr_ge2, LDS bytes}
+ *            (the DcnHaloSel of each launch: counter indices, -1 = condition absent; unused slots 0), grid x, y, z, LDS bytes};
+ *   backward plan[41] = {input-gradient family (0 none, 1 dcn_bwdin6<NK>, 2 dcn_bwd_input_kernel<CHS>; -1 refused), NK, terms, CHS,
+ *            LDS bytes of dcn_bwd_input_kernel, dcn_bwdin6 runs its own probe pass, launches (1-5), 5 x {window, ge, lt, threshold},
+ *            hand-off written, its byte offset in the workspace, weight-gradient family (0 none, 1 dcn_bwdw6<R, TH>, 2 dcn_bwdw4<NT>,
+ *            3 dcn_bwdw2_kernel, 4 dcn_bwd_weight_kernel<0>), R, TH, terms, ns, nmb, xcd, P, Q (partials), gy, gz, LDS bytes}.
+ * The developer switches (RVSR_DCN_BWD, RVSR_DCN5_HALO, RVSR_DCN3_HALO, RVSR_BWDW6_WG; read once per process) enter as in the call. */
+int rvsr_dcn_pack_forward_plan(const float* input, const float* weight, const float* bias, const float* om,
+                               float* output, int batch, int channels, int height, int width, int channels_out,
+                               int stride, int pad, int dilation, int deformable_group, int act, float slope,
+                               void* probe, void* workspace, size_t workspace_bytes, long long* plan);
+int rvsr_dcn_pack_backward_plan(const float* input, const float* weight, const float* om, const float* grad_output,
+                                const float* act_out, float act_slope, float* grad_input, float* grad_weight,
+                                float* grad_bias, float* grad_om, int batch, int channels, int height, int width,
+                                int channels_out, int stride, int pad, int dilation, int deformable_group,
+                                const void* probe, void* workspace, size_t workspace_bytes, long long* plan);
+/* Three rules of csrc/dcn_plan.h for the host glue (no GPU needed): the code with which the fused entries of sections 1 / 1b answer a
+ * geometry (RVSR_OK: taken); the number of samples behind the counters of rvsr_dcn_offset_probe; and the tile halo (3 / 7 / 11; 0: no
+ * samples) that a forward with channels_out output channels selects on the device from such counters -- `counters`: 6 uint32 in HOST
+ * memory -- so that a caller who kept them can pass the same choice as the hint of a later step. */
+int rvsr_dcn_fused_takes(int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w, int stride_h,
+                         int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int group, int deformable_group);
+size_t rvsr_dcn_probe_samples(int batch, int deformable_group, int height_out, int width_out);
+int rvsr_dcn_forward_halo(const unsigned* counters, size_t nsamples, int channels_out);
 
 /* 1c. The operator over its whole argument space: any kernel_h x kernel_w, anisotropic stride / padding / dilation, group >= 1, any
  * number of channels per deformable group, DCNv1 (mask == NULL) and DCNv2, element types f32 / f64 / f16 (dtype 0 / 1 / 2) -- what

@@ -38,6 +38,12 @@ SIGNATURES = {
     'rvsr_dcn_pack_forward': (c_int, [c_fp] * 5 + [c_int] * 10 + [c_float, c_fp, c_fp, c_size, c_fp]),
     'rvsr_dcn_offset_probe': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     'rvsr_dcn_pack_backward': (c_int, [c_fp] * 5 + [c_float] + [c_fp] * 4 + [c_int] * 9 + [c_fp, c_fp, c_size, c_fp]),
+    'rvsr_dcn_pack_forward_plan': (c_int, [c_fp] * 5 + [c_int] * 10 + [c_float, c_fp, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong)]),
+    'rvsr_dcn_pack_backward_plan': (c_int, [c_fp] * 5 + [c_float] + [c_fp] * 4 + [c_int] * 9 + [c_fp, c_fp, c_size,
+                                                                                             ctypes.POINTER(ctypes.c_longlong)]),
+    'rvsr_dcn_fused_takes': (c_int, [c_int] * 15),
+    'rvsr_dcn_probe_samples': (c_size, [c_int] * 4),
+    'rvsr_dcn_forward_halo': (c_int, [c_fp, c_size, c_int]),
     'rvsr_conv2d_forward': (c_int, _CONV_CALL + [c_fp, c_size, c_fp]),
     'rvsr_conv2d_forward_plan': (c_int, _CONV_CALL + [ctypes.POINTER(c_int)]),
     'rvsr_conv2d_forward_workspace_bytes': (c_size, [c_int] * 4),

@@ -208,8 +208,8 @@ class DcnOffsetStats:
     has N).  Without an optimizer that calls advance() the lag is counted in backwards of the layer instead.  Offsets of a layer change
     slowly from step to step, and the choice affects speed and the last bits of rounding only (samples beyond the tile gather from global
     memory with the same rules) -- which also means that data-parallel ranks, whose offsets differ, may run different tile sizes: their
-    forwards are equal to rounding, not bitwise.  Rule = the device-side rule of rvsr_launch_dcn_fwd3: 3 px while < 8 % of the components
-    exceed 3.5 px, 7 px while < 1 % exceed 7.5 px, else 11 px (7 px above 64 output channels)."""
+    forwards are equal to rounding, not bitwise.  The rule is the device's: rvsr_dcn_forward_halo evaluates the candidates of the forward
+    plan (csrc/dcn_plan.h) on the copied counters."""
     LAG = 3
 
     def __init__(self):
@@ -249,15 +249,7 @@ class DcnOffsetStats:
         if slot.tick not in layer.halo:
             c, n = slot.counters, slot.nsamples
             slot.event.synchronize()
-            if n == 0:
-                halo = 0
-            elif int(c[1]) * 100 < 8 * n:
-                halo = 3
-            elif int(c[3]) * 100 < n or Co > 64:
-                halo = 7
-            else:
-                halo = 11
-            layer.halo = {slot.tick: halo}
+            layer.halo = {slot.tick: _lib.lib().rvsr_dcn_forward_halo(c.data_ptr(), n, Co)}
         return layer.halo[slot.tick]
 
 

@@ -32,6 +32,7 @@ extern "C" int rvsr_debug_read_dcn(unsigned long long* out) { return (int)hipMem
 #endif
 
 #include "dcn_tile.h"
+#include "dcn_plan.h"
 
 template <int TH, int MT>
 __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(const DcnFwdParams p, const bf16x8* __restrict__ wpack) {
@@ -192,69 +193,46 @@ __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------
-static void fwd2_geom(int Co, int C, int& mt, int& nchunks, int& nmb) {
-    mt = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
-    nchunks = (C + 15) / 16;
-    nmb = (Co + mt * 32 - 1) / (mt * 32);
-}
-
-static size_t fwd2_image_bytes(int Co, int C) {
-    int mt, nchunks, nmb;
-    fwd2_geom(Co, C, mt, nchunks, nmb);
-    return (size_t)nmb * nchunks * 2 * 9 * 2 * (mt * 32) * 16;
-}
-size_t rvsr_dcn_fwd2_workspace_bytes(int Co, int C) { return fwd2_image_bytes(Co, C); }
 template <int TH, int MT>
-static int launch_dcn_fwd2(const DcnFwdParams& p, const bf16x8* wpack, hipStream_t st) {
-    constexpr int TR = TH + 2 * D2_R + 2, TC = 32 + 2 * D2_R + 2;
-    const size_t lds = (size_t)16 * (4 * TR * TC + 2 * 9 * 2 * MT * 32) + sizeof(float) * MT * 32;
+static int launch_dcn_fwd2(const DcnFwdParams& p, const DcnFwdPlan& q, const bf16x8* wpack, hipStream_t st) {
     auto k = dcn_fwd2_kernel<TH, MT>;
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd2: cannot reserve %zu B of LDS", lds);
-    const DcnGeom& d = p.d;
-    dim3 grid(d.ntx * ((d.Ho + TH - 1) / TH), (d.Co + MT * 32 - 1) / (MT * 32), d.B);
-    hipLaunchKernelGGL(k, grid, dim3(TH * 64), lds, st, p, wpack);
+    if (set_lds(k, q.lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd2: cannot reserve %zu B of LDS", q.lds);
+    hipLaunchKernelGGL(k, dim3(q.gx, q.gy, q.gz), dim3(TH * 64), q.lds, st, p, wpack);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd2 launch: %s", hipGetErrorString(e));
     return RVSR_OK;
 }
+int rvsr_launch_dcn_fwd2(const DcnFwdParams& p, const DcnFwdPlan& q, const void* wpack, hipStream_t st) {
+    const bf16x8* wp = (const bf16x8*)wpack;
+    switch (q.mt) {
+        case 1: return launch_dcn_fwd2<8, 1>(p, q, wp, st);
+        case 2: return launch_dcn_fwd2<8, 2>(p, q, wp, st);
+        default: return launch_dcn_fwd2<8, 4>(p, q, wp, st);
+    }
+}
 
-// the forward's weight image in caller-owned memory (+ its descriptor for rvsr_pack_weights_batched), see include/realvsr_hip.h
+// the forward's weight image (dcn_fwd2_geom, dcn_plan.h)
+static void launch_dcn_pack(const float* weight, int Co, int C, void* out, hipStream_t st) {
+    int mt, nchunks, nmb;
+    dcn_fwd2_geom(Co, C, mt, nchunks, nmb);
+    const size_t total = (size_t)nmb * nchunks * 9 * 2 * (mt * 32);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, weight, (bf16x8*)out, Co, C, 9, mt * 32, 1,
+                       nchunks, nmb, 0);
+}
+void rvsr_launch_dcn_fwd_pack(const DcnFwdParams& p, void* wpack, hipStream_t st) { launch_dcn_pack(p.w, p.d.Co, p.d.C, wpack, st); }
+// ... in caller-owned memory (+ its descriptor for rvsr_pack_weights_batched), see include/realvsr_hip.h
 extern "C" size_t rvsr_dcn_pack_weights(const float* weight, int C, int Co, void* out, size_t out_bytes, long long* desc, void* stream) {
     int mt, nchunks, nmb;
-    fwd2_geom(Co, C, mt, nchunks, nmb);
-    const size_t need = rvsr_dcn_fwd2_workspace_bytes(Co, C);
+    dcn_fwd2_geom(Co, C, mt, nchunks, nmb);
+    const size_t need = dcn_fwd2_image_bytes(Co, C);
     if (!weight || !out || out_bytes < need) return 0;
-    const size_t total = (size_t)nmb * nchunks * 9 * 2 * (mt * 32);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, (bf16x8*)out, Co,
-                       C, 9, mt * 32, 1, nchunks, nmb, 0);
+    launch_dcn_pack(weight, Co, C, out, (hipStream_t)stream);
     if (desc) {
         desc[0] = (long long)(uintptr_t)weight; desc[1] = (long long)(uintptr_t)out;
         desc[2] = Co; desc[3] = C; desc[4] = 9; desc[5] = mt * 32; desc[6] = 1; desc[7] = nchunks; desc[8] = nmb; desc[9] = 0;
     }
     if (desc) for (int i = 10; i < 20; ++i) desc[i] = 0;   // (second descriptor: the slot of the removed dcn_fwd4 image, kept zero for the ABI)
     return need;
-}
-
-int rvsr_launch_dcn_fwd2(const DcnFwdParams& p, void* workspace, size_t workspace_bytes, hipStream_t st, const unsigned* probe, size_t nprobe, int halo_hint) {
-    const DcnGeom& d = p.d;
-    if (d.cpg % 8 != 0) return RVSR_ERR_UNSUPPORTED;  // a k-octet must lie inside one deformable group
-    int mt, nchunks, nmb;
-    fwd2_geom(d.Co, d.C, mt, nchunks, nmb);
-    const size_t need = rvsr_dcn_fwd2_workspace_bytes(d.Co, d.C);
-    if (!workspace || workspace_bytes < need) FAIL(RVSR_ERR_WORKSPACE, "dcn forward: workspace %zu B < %zu B", workspace_bytes, need);
-    const size_t total = (size_t)nmb * nchunks * 9 * 2 * (mt * 32);
-    if (!p.prepacked) {
-        hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.w, (bf16x8*)workspace, d.Co,
-                           d.C, 9, mt * 32, 1, nchunks, nmb, 0);
-    }
-    const bf16x8* wp = (const bf16x8*)workspace;
-    {   // third generation where it covers the geometry (stride 1, dilation 1); else the second
-        const int rc = rvsr_launch_dcn_fwd3(p, workspace, mt, st, probe, nprobe, halo_hint);
-        if (rc != RVSR_ERR_UNSUPPORTED) return rc;
-    }
-    if (mt == 1) return launch_dcn_fwd2<8, 1>(p, wp, st);
-    if (mt == 2) return launch_dcn_fwd2<8, 2>(p, wp, st);
-    return launch_dcn_fwd2<8, 4>(p, wp, st);
 }
 
 // ==========================================================================================
@@ -467,30 +445,14 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
 
 #include "dcn_bwdw4.inc"
 
-// returns the number of partials written (8 * P), or -1 if the geometry is not covered
-int rvsr_launch_dcn_bwdw2(const DcnGeom& d, const TView& g, float* part, float* bpart_or_null, int P, int nty, int gy, int gz,
-                          hipStream_t st) {
-    if (d.cpg % 8 != 0) return -1;
+// dcn_bwdw4<NT> (bf16 split products) or the exact-f32 dcn_bwdw2_kernel, as planned: 8 * P partials
+int rvsr_launch_dcn_bwdw2(const DcnGeom& d, const DcnBwdPlan& q, const TView& g, float* part, float* bpart, hipStream_t st) {
     DcnBwdW2Params p;
-    p.d = d; p.g = g; p.part = part; p.bpart = bpart_or_null; p.P = P; p.nty = nty;
-    p.gvec = ((((uintptr_t)g.p) | ((uintptr_t)g.act)) & 15) == 0;
-    constexpr int TR = 4 + 2 * D2_R + 2, TC = 32 + 2 * D2_R + 2;
-    if (rvsr_gemm_mode_now() != 1) {  // bf16 split products
-        const size_t lds3 = (size_t)16 * 2 * TR * TC + (size_t)2 * (64 + 96) * 272;
-        // (dcn_bwdw4 addresses 64 gOut planes, 27 offset / mask planes and 8 x planes with 32-bit byte offsets inside 2 GB buffer views)
-        const bool spans_ok = (size_t)256 * d.Ho * d.Wo < ((size_t)1 << 31) && (size_t)32 * d.H * d.W < ((size_t)1 << 31);
-        if (d.stride == 1 && d.dil == 1 && g.mode == 0 && (d.Wo & 3) == 0 && p.gvec && spans_ok) {
-            const int nt = rvsr_gemm_terms();   // reduced-term products (gemm modes 2 / 3)
-            auto k4 = nt == 2 ? dcn_bwdw4_kernel<2> : (nt == 1 ? dcn_bwdw4_kernel<1> : dcn_bwdw4_kernel<3>);
-            if (set_lds(k4, lds3)) return -2;
-            hipLaunchKernelGGL(k4, dim3(P, gy, gz), dim3(512), lds3, st, p);
-            return 8 * P;
-        }
-        // (views / geometries dcn_bwdw4 does not take: the exact-f32 kernel below)
-    }
-    const size_t lds = (size_t)16 * 2 * TR * TC + sizeof(float) * (DCN_NPX * 65 + DCN_NPX * 97);
-    if (set_lds(dcn_bwdw2_kernel, lds)) return -2;
-    hipLaunchKernelGGL(dcn_bwdw2_kernel, dim3(P, gy, gz), dim3(512), lds, st, p);
-    return 8 * P;
+    p.d = d; p.g = g; p.part = part; p.bpart = bpart; p.P = q.P; p.nty = (d.Ho + 3) / 4;
+    p.gvec = q.g_vec;
+    auto k = dcn_bwdw2_kernel;
+    if (q.w_family == DCN_BWDW4) k = q.w_nt == 2 ? dcn_bwdw4_kernel<2> : (q.w_nt == 1 ? dcn_bwdw4_kernel<1> : dcn_bwdw4_kernel<3>);
+    if (set_lds(k, q.w_lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwdw2: cannot reserve LDS");
+    hipLaunchKernelGGL(k, dim3(q.P, q.gy, q.gz), dim3(512), q.w_lds, st, p);
+    return RVSR_OK;
 }
-

@@ -16,6 +16,7 @@
 // Geometry: stride 1, dilation 1, groups of >= 8 channels (what EDVR / TDAN instantiate); everything else keeps the
 // second-generation kernel.
 #include "dcn_tile.h"
+#include "dcn_plan.h"
 
 #ifdef RVSR_TIMELINE_DCN
 __device__ unsigned long long rvsr_dbg_dcn3[256];
@@ -374,74 +375,36 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
     TSTAMP(30);
 }
 
-template <int MT, int R>
-static int launch_dcn_fwd3(const DcnFwdParams& p, const bf16x8* wpack, hipStream_t st) {
-    constexpr int TH = 8, TR = TH + 2 * R + 2, TC = 32 + 2 * R + 2;
-    const size_t lds = (size_t)16 * (4 * TR * TC + 2 * 9 * 2 * MT * 32) + sizeof(float) * MT * 32;
-    auto k = dcn_fwd3_kernel<MT, R>;
-    if constexpr (MT >= 2) {   // reduced-term products (gemm modes 2 / 3): the kernels of the nf64 / nf128 packs
-        const int nt = rvsr_gemm_terms();
-        if (nt == 2) k = dcn_fwd3_kernel<MT, R, 2>;
-        if (nt == 1) k = dcn_fwd3_kernel<MT, R, 1>;
-    }
+template <int MT, int R, int TERMS>
+static int launch_dcn_fwd3(const DcnFwdParams& p, const DcnFwdPlan& q, size_t lds, const bf16x8* wpack, hipStream_t st) {
+    auto k = dcn_fwd3_kernel<MT, R, TERMS>;
     if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd3: cannot reserve %zu B of LDS", lds);
-    const DcnGeom& d = p.d;
-    dim3 grid(d.ntx * ((d.Ho + TH - 1) / TH), (d.Co + MT * 32 - 1) / (MT * 32), d.B);
-    hipLaunchKernelGGL(k, grid, dim3(TH * 64), lds, st, p, wpack);
+    hipLaunchKernelGGL(k, dim3(q.gx, q.gy, q.gz), dim3(512), lds, st, p, wpack);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd3 launch: %s", hipGetErrorString(e));
     return RVSR_OK;
 }
-template <int MT>
-static int launch_dcn_fwd3_halo(const DcnFwdParams& p, const bf16x8* wpack, int halo, hipStream_t st) {
-    if (halo <= 3) return launch_dcn_fwd3<MT, 3>(p, wpack, st);
-    if (halo <= 7) return launch_dcn_fwd3<MT, 7>(p, wpack, st);
-    if constexpr (MT <= 2) return launch_dcn_fwd3<MT, 11>(p, wpack, st);   // (11 px + the 74 KB weight slice of MT = 4 exceed 160 KB)
-    return launch_dcn_fwd3<MT, 7>(p, wpack, st);
-}
 
-// `wpack`: the image pack_weights_kernel(mode 0, CCG 1) wrote for (mt, nchunks, nmb) -- built by rvsr_launch_dcn_fwd2's caller.
-// `probe` (nullable): the three device counters of dcn_offset_probe2_kernel for this call's offsets: the halo is then chosen on the device.
-int rvsr_launch_dcn_fwd3(const DcnFwdParams& p_in, const void* wpack, int mt, hipStream_t st, const unsigned* probe, size_t nprobe, int halo_hint) {
+// `wpack`: the image pack_weights_kernel(mode 0, CCG 1) wrote for the plan's MT.  One launch per candidate halo of the plan; with more than
+// one, each reads the counters of dcn_offset_probe2_kernel for this call's offsets at `probe` and returns at once unless it is the selected one.
+int rvsr_launch_dcn_fwd3(const DcnFwdParams& p_in, const DcnFwdPlan& q, const void* wpack, const unsigned* probe, hipStream_t st) {
     DcnFwdParams p = p_in;
-    const DcnGeom& d = p.d;
-    if (d.cpg % 8 != 0 || d.stride != 1 || d.dil != 1) return RVSR_ERR_UNSUPPORTED;
-    // 32-bit byte offsets into one batch element's x / offset / output planes: larger frames take dcn_fwd2
-    const size_t planes = (size_t)(d.C / d.cpg) * 18 > (size_t)(d.C > d.Co ? d.C : d.Co) ? (size_t)(d.C / d.cpg) * 18 : (size_t)(d.C > d.Co ? d.C : d.Co);
-    if (planes * d.H * d.W * sizeof(float) >= ((size_t)1 << 32)) return RVSR_ERR_UNSUPPORTED;
     const bf16x8* wp = (const bf16x8*)wpack;
-    static const int fixed = [] { const char* e = getenv("RVSR_DCN3_HALO"); return e ? atoi(e) : -1; }();   // developer A/B switch
-    const bool big_ok = (d.W % 4 == 0) && ((((uintptr_t)d.x) & 15) == 0) && (size_t)d.C * d.H * d.W * sizeof(float) < ((size_t)1 << 31);
-    p.sel = dcn_halo_always();
-    int rc = RVSR_OK;
-#define FWD3_DISPATCH(HALO)                                                        \
-    do {                                                                           \
-        if (mt == 1) rc = launch_dcn_fwd3_halo<1>(p, wp, HALO, st);                \
-        else if (mt == 2) rc = launch_dcn_fwd3_halo<2>(p, wp, HALO, st);           \
-        else rc = launch_dcn_fwd3_halo<4>(p, wp, HALO, st);                        \
-    } while (0)
-    if (fixed >= 0 || probe == nullptr || !big_ok) {
-        // no counters: the caller's hint (a halo chosen on the host from an earlier statistic of this layer's offsets), else 3 px
-        FWD3_DISPATCH(big_ok ? (fixed >= 0 ? fixed : (halo_hint > 0 ? halo_hint : 3)) : 3);
-        return rc;
+    for (int k = 0; k < q.ncand; ++k) {
+        const DcnHaloCand& c = q.cand[k];
+        p.sel = dcn_cand_sel(c, probe);
+        int rc = RVSR_ERR_LAUNCH;
+#define FWD3(MT, R, NT) case (MT * 100 + R) * 10 + NT: rc = launch_dcn_fwd3<MT, R, NT>(p, q, c.lds, wp, st); break
+#define FWD3_TERMS(MT, R) FWD3(MT, R, 3); FWD3(MT, R, 2); FWD3(MT, R, 1)
+        switch ((q.mt * 100 + c.halo) * 10 + q.nt) {   // the kernels that are built
+            FWD3(1, 3, 3); FWD3(1, 7, 3); FWD3(1, 11, 3);
+            FWD3_TERMS(2, 3); FWD3_TERMS(2, 7); FWD3_TERMS(2, 11);
+            FWD3_TERMS(4, 3); FWD3_TERMS(4, 7);
+            default: FAIL(RVSR_ERR_LAUNCH, "dcn_fwd3: no kernel <%d, %d, %d>", q.mt, c.halo, q.nt);
+        }
+#undef FWD3_TERMS
+#undef FWD3
+        if (rc != RVSR_OK) return rc;
     }
-    // The smallest tile that leaves (almost) no sample outside: a k-step in which ANY of a wave's 64 lanes left the tile pays the global
-    // gather for all of them, and at one workgroup per CU the large tiles hide that latency worse than the small one -- measured
-    // (profiles/r03_notes.md): a 7 px halo with 10 % of the samples outside is slower than the 3 px halo with 65 % outside.
-    //   R = 3: < 8 % of the offset components beyond 3.5 px;  R = 7: else, < 1 % beyond 7.5 px (or no larger tile);  R = 11: the rest
-    // (crossovers of the fixed-halo timings at offset std 1.25 / 2.5 / 3.75 / 6.25 px; caches.DcnOffsetStats applies the same rule
-    // on the host to the counters of the previous step).
-    const unsigned thr3 = (unsigned)(nprobe * 8 / 100) + 1, thr7 = (unsigned)(nprobe / 100) + 1;
-    const bool has11 = mt <= 2;
-    p.sel.probe = probe;
-    p.sel.ge = -1; p.sel.lt = 1; p.sel.thr_lt = thr3;
-    FWD3_DISPATCH(3);
-    if (rc != RVSR_OK) return rc;
-    p.sel.ge = 1; p.sel.thr_ge = thr3; p.sel.lt = has11 ? 3 : -1; p.sel.thr_lt = thr7;
-    FWD3_DISPATCH(7);
-    if (rc != RVSR_OK || !has11) return rc;
-    p.sel.ge = 3; p.sel.thr_ge = thr7; p.sel.lt = -1; p.sel.ge2 = 1; p.sel.thr_ge2 = thr3;   // (a partition: not when R = 3 runs)
-    FWD3_DISPATCH(11);
-#undef FWD3_DISPATCH
-    return rc;
+    return RVSR_OK;
 }

@@ -39,6 +39,7 @@
 // core -- is numerically right and kept as experiments/dcn_bwd6_fused.hip; it needs ~400 live registers per wave and ran 16 ms per L1
 // launch against 7.3 for the pair: profiles/r05_notes.md.)
 #include "dcn_tile.h"
+#include "dcn_plan.h"
 
 #ifdef RVSR_TIMELINE_DCN6   // s_memtime stamps of one wave of one workgroup (tools/dcn6_timeline.py); [0, 128): dcn_bwdin6, [128, 256): dcn_bwdw6
 __device__ unsigned long long rvsr_dbg_dcn6[256];
@@ -680,41 +681,16 @@ __global__ void dcn_offset_probe2_kernel(const float* __restrict__ off, size_t o
     }
 }
 
-static size_t dcn_probe_samples(const DcnGeom& d) { return (size_t)d.B * ((d.C / d.cpg) * 18) * ((d.Ho + 15) / 16) * d.Wo; }
 // memset-free: the caller zeroes the counters (a fresh torch.zeros in the Python layer, hipMemsetAsync in the backward's own path)
-size_t rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st) {
+void rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st) {
     const int oplanes = (d.C / d.cpg) * 18;
-    const size_t nprobe = dcn_probe_samples(d);
+    const size_t nprobe = dcn_probe_samples(d.B, d.C / d.cpg, d.Ho, d.Wo);
     const unsigned nb = (unsigned)((nprobe + 2047) / 2048 < 2048 ? (nprobe + 2047) / 2048 : 2048);
     hipLaunchKernelGGL(dcn_offset_probe2_kernel, dim3(nb ? nb : 1), dim3(256), 0, st, d.offset, d.off_bs, d.B, oplanes, d.Ho, d.Wo, cnt);
-    return nprobe;
 }
-
-// One batch element's planes are addressed with 32-bit byte offsets (x through a 2 GB view: bit 31 marks the zero padding).
-static bool dcn_planes_below_2g(const DcnGeom& d) {
-    const size_t oplanes = (size_t)(d.C / d.cpg) * 18, planes = oplanes > (size_t)d.C ? oplanes : (size_t)d.C, lim = (size_t)1 << 31;
-    return planes * (size_t)d.H * d.W * sizeof(float) < lim && planes * (size_t)d.Ho * d.Wo * sizeof(float) < lim;
-}
-// The geometries dcn_bwdin6 takes; every other call takes the first-generation dcn_bwd_input_kernel.
-bool rvsr_dcn_bwdin6_takes(const DcnGeom& d) {
-    return d.cpg % 8 == 0 && d.C % 8 == 0 && d.stride == 1 && d.dil == 1 && d.Co <= 128 && dcn_planes_below_2g(d);
-}
-
-static int nk6_of(int Co) { return Co <= 16 ? 1 : (Co <= 32 ? 2 : (Co <= 64 ? 4 : 8)); }
-// dcn_bwdin6's share of the backward's workspace, byte offsets: the packed weight image at 0, the per-chunk column norms, the probe's counters
-struct Bwdin6Workspace { size_t wnorm, probe, total; };
-static Bwdin6Workspace bwdin6_workspace(int Co, int C) {
-    const size_t nchunks = (size_t)((C + 7) / 8);
-    Bwdin6Workspace w;
-    w.wnorm = nchunks * 3 * 2 * (2 * nk6_of(Co)) * 32 * 16;
-    w.probe = w.wnorm + ((nchunks * 4 + 255) & ~(size_t)255);
-    w.total = w.probe + 256;
-    return w;
-}
-size_t rvsr_dcn_bwdin6_workspace_bytes(int Co, int C) { return bwdin6_workspace(Co, C).total; }
 
 template <int NK, int R>
-static int launch_bwdin6(const DcnBwdIn6Params& p, const bf16x8* wpack, hipStream_t st) {
+static int launch_bwdin6(const DcnBwdIn6Params& p, int nt, const bf16x8* wpack, hipStream_t st) {
     constexpr int TH = 8, TR = TH + 2 * R + 3, TC = 32 + 2 * R + 3, NPOS = TR * TC;
     constexpr size_t wbytes = (size_t)3 * 2 * (2 * NK) * 32 * 16;
     constexpr size_t lds1 = (size_t)NPOS * (2 * 16 + 8 * 4) + wbytes + 8 * sizeof(float);
@@ -729,7 +705,6 @@ static int launch_bwdin6(const DcnBwdIn6Params& p, const bf16x8* wpack, hipStrea
     constexpr int WPS = 2;   // waves per SIMD the launch bounds name: ONE 8-wave workgroup per CU (~220 registers per lane)
     auto k = dcn_bwdin6_kernel<NK, R, 3, WPS, W2, G2>;
     if constexpr (NK >= 4) {   // reduced-term products (gemm modes 2 / 3): the kernels of the nf64 / nf128 packs
-        const int nt = rvsr_gemm_terms();
         if (nt == 2) k = dcn_bwdin6_kernel<NK, R, 2, WPS, W2, G2>;
         if (nt == 1) k = dcn_bwdin6_kernel<NK, R, 1, WPS, W2, G2>;
     }
@@ -742,31 +717,18 @@ static int launch_bwdin6(const DcnBwdIn6Params& p, const bf16x8* wpack, hipStrea
     return RVSR_OK;
 }
 
-template <int NK>
-static int launch_bwdin6_halo(const DcnBwdIn6Params& p, const bf16x8* wpack, int halo, hipStream_t st) {
-    if (halo <= 2) return launch_bwdin6<NK, 2>(p, wpack, st);
-    if (halo <= 4) return launch_bwdin6<NK, 4>(p, wpack, st);
-    if (halo <= 5) return launch_bwdin6<NK, 5>(p, wpack, st);
-    if (halo <= 8) return launch_bwdin6<NK, 8>(p, wpack, st);
-    if constexpr (NK <= 4) return launch_bwdin6<NK, 12>(p, wpack, st);   // (12 px + the 48 KB weight block of NK = 8 exceed 160 KB)
-    return launch_bwdin6<NK, 8>(p, wpack, st);
-}
-
-// halo < 0: selected on the device from the offsets (probe + one launch per candidate halo, no host round trip).
-// RVSR_ERR_UNSUPPORTED (geometry not taken, or no workspace): the caller falls back to the first-generation kernel.
-int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
-                           float* gmask, size_t gmask_bs, void* workspace, size_t workspace_bytes, hipStream_t st, int halo,
-                           const unsigned* probe_in, void* agt) {
+// The column norms and the packed weight image into the workspace, then one launch per candidate window of the plan; with more than one, each
+// reads the offset counters (the caller's `probe`, else its own probe pass into the workspace) and returns at once unless it is the selected one.
+int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const DcnBwdPlan& q, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
+                           float* gmask, size_t gmask_bs, void* workspace, const unsigned* probe, hipStream_t st) {
     const Bwdin6Workspace lay = bwdin6_workspace(d.Co, d.C);
-    if (!rvsr_dcn_bwdin6_takes(d) || !workspace || workspace_bytes < lay.total) return RVSR_ERR_UNSUPPORTED;
-    const int NK = nk6_of(d.Co), nchunks = (d.C + 7) / 8;
+    const int nchunks = (d.C + 7) / 8;
     bf16x8* wpack = (bf16x8*)workspace;
     float* wnorm = (float*)((unsigned char*)workspace + lay.wnorm);
-    unsigned* cnt = (unsigned*)((unsigned char*)workspace + lay.probe);
     hipLaunchKernelGGL(dcn_bwd5_wnorm_kernel, dim3(nchunks), dim3(576), 0, st, weight, wnorm, d.Co, d.C);
-    const size_t total = (size_t)nchunks * 3 * (2 * NK) * 32;
+    const size_t total = (size_t)nchunks * 3 * (2 * q.nk) * 32;
     const dim3 pg((unsigned)((total + 255) / 256)), pb(256);
-    switch (NK) {
+    switch (q.nk) {
         case 1: hipLaunchKernelGGL(pack_weights_bwd6_kernel<1>, pg, pb, 0, st, weight, wpack, d.Co, d.C, nchunks); break;
         case 2: hipLaunchKernelGGL(pack_weights_bwd6_kernel<2>, pg, pb, 0, st, weight, wpack, d.Co, d.C, nchunks); break;
         case 4: hipLaunchKernelGGL(pack_weights_bwd6_kernel<4>, pg, pb, 0, st, weight, wpack, d.Co, d.C, nchunks); break;
@@ -774,52 +736,32 @@ int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g
     }
     DcnBwdIn6Params p;
     p.d = d; p.g = g; p.gx = gx; p.goff = goff; p.gmask = gmask; p.goff_bs = goff_bs; p.gmask_bs = gmask_bs;
-    p.sel = dcn_halo_always(); p.wnorm = wnorm;
-    p.agt = (bf16x8*)agt; p.agt_nmb32 = 2 * ((d.Co + 63) / 64); p.agt_rows = ((d.Ho + 7) / 8) * 8;
-#define BWDIN6_DISPATCH(HALO)                                                   \
-    switch (NK) {                                                               \
-        case 1: rc = launch_bwdin6_halo<1>(p, wpack, HALO, st); break;          \
-        case 2: rc = launch_bwdin6_halo<2>(p, wpack, HALO, st); break;          \
-        case 4: rc = launch_bwdin6_halo<4>(p, wpack, HALO, st); break;          \
-        default: rc = launch_bwdin6_halo<8>(p, wpack, HALO, st); break;         \
-    }
-    int rc = RVSR_OK;
-    if (halo >= 0) {
-        BWDIN6_DISPATCH(halo);
-        return rc;
-    }
-    const size_t nprobe = dcn_probe_samples(d);
-    if (probe_in != nullptr) {
-        cnt = const_cast<unsigned*>(probe_in);   // the forward of this layer already counted these offsets (rvsr_dcn_pack_forward's probe)
-    } else {
+    p.wnorm = wnorm;
+    p.agt = q.handoff ? (bf16x8*)((unsigned char*)workspace + q.handoff_off) : nullptr;
+    p.agt_nmb32 = 2 * ((d.Co + 63) / 64); p.agt_rows = ((d.Ho + 7) / 8) * 8;
+    if (q.own_probe) {
+        unsigned* cnt = (unsigned*)((unsigned char*)workspace + lay.probe);
         if (hipMemsetAsync(cnt, 0, DCN_PROBE_COUNTERS * sizeof(unsigned), st) != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn backward: memset of the probe counters failed");
         rvsr_launch_dcn_offset_probe(d, cnt, st);
-    }
-    // A sample beyond the halo costs 32 global gathers + 32 global atomics, a larger halo costs staging and flush work in proportion to its
-    // cells (585 / 817 / 945 / 1377 / 2065): switch up as soon as 2 % of the offset components leave the smaller window.
-    const unsigned thr = (unsigned)(nprobe * (size_t)2 / 100) + 1;
-    const bool has12 = NK <= 4;
-    p.sel.probe = cnt;
-    p.sel.thr_ge = p.sel.thr_lt = thr;
-    // R = 2: few components beyond 2.5 px; R = 4: else, few beyond 3.5 px; R = 5: else, few beyond 5.5; R = 8: else, few beyond 8.5 (or no
-    // larger window); R = 12: the rest.  The counters are monotone, so the chain is a partition.
-    if (has12) {
-        const int halos[5] = {2, 4, 5, 8, 12}, ge[5] = {-1, 0, 1, 2, 4}, lt[5] = {0, 1, 2, 4, -1};
-        for (int k = 0; k < 5; ++k) {
-            p.sel.ge = ge[k]; p.sel.lt = lt[k];
-            BWDIN6_DISPATCH(halos[k]);
-            if (rc != RVSR_OK) return rc;
+        probe = cnt;
+    }   // (else: the forward of this layer already counted these offsets, rvsr_dcn_pack_forward's probe)
+    for (int k = 0; k < q.ncand; ++k) {
+        p.sel = dcn_cand_sel(q.cand[k], probe);
+        int rc = RVSR_ERR_LAUNCH;
+#define BWDIN6(NK, R) case NK * 100 + R: rc = launch_bwdin6<NK, R>(p, q.in_nt, wpack, st); break
+#define BWDIN6_TO8(NK) BWDIN6(NK, 2); BWDIN6(NK, 4); BWDIN6(NK, 5); BWDIN6(NK, 8)
+        switch (q.nk * 100 + q.cand[k].halo) {   // the kernels that are built
+            BWDIN6_TO8(1); BWDIN6(1, 12);
+            BWDIN6_TO8(2); BWDIN6(2, 12);
+            BWDIN6_TO8(4); BWDIN6(4, 12);
+            BWDIN6_TO8(8);
+            default: FAIL(RVSR_ERR_LAUNCH, "dcn_bwdin6: no kernel <%d, %d>", q.nk, q.cand[k].halo);
         }
-    } else {
-        const int halos[4] = {2, 4, 5, 8}, ge[4] = {-1, 0, 1, 2}, lt[4] = {0, 1, 2, -1};
-        for (int k = 0; k < 4; ++k) {
-            p.sel.ge = ge[k]; p.sel.lt = lt[k];
-            BWDIN6_DISPATCH(halos[k]);
-            if (rc != RVSR_OK) return rc;
-        }
+#undef BWDIN6_TO8
+#undef BWDIN6
+        if (rc != RVSR_OK) return rc;
     }
-#undef BWDIN6_DISPATCH
-    return rc;
+    return RVSR_OK;
 }
 
 // ==========================================================================================================================================
@@ -1132,65 +1074,20 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
     }
 }
 
-// streams (= partials) of a launch with `wpc` workgroups per CU; 0: more (chunk, 64 output channels) units than the 256 CUs, not covered
-static int bwdw6_streams(int Co, int C, int wpc, int* nmb_out, int* xcd_out) {
-    const int nchunks = C / 8, nmb = (Co + 63) / 64, U = nchunks * nmb;
-    if (U <= 0 || U > 256) return 0;
-    if (nmb_out) *nmb_out = nmb;
-    if (xcd_out) *xcd_out = 32 % U == 0 ? 1 : 0;
-    return 256 * wpc / U > 0 ? 256 * wpc / U : 1;
-}
-// Developer switch RVSR_BWDW6_WG=2: two workgroups of four waves per CU (4-row tiles, 2 px window) instead of one of eight (8-row tiles, 4 px
-// window) -- the configuration whose run-to-run differences round 5 could not explain; kept selectable so that the determinism test covers it
-// (profiles/r06_notes.md).
-static int bwdw6_wpc() {
-    static const int v = [] { const char* e = getenv("RVSR_BWDW6_WG"); return e && atoi(e) == 2 ? 2 : 1; }();
-    return v;
-}
-size_t rvsr_dcn_bwdw6_workspace_bytes(int Co, int C) {
-    const int ns = bwdw6_streams(Co, C, 2, nullptr, nullptr);   // (sized for either schedule)
-    return (size_t)ns * ((size_t)Co * C * 9 + Co) * sizeof(float) + 256;
-}
-// the operand buffer dcn_bwdin6 writes for dcn_bwdw6: one 16-byte vector per (row, x tile, 32 output channels, k-step, hi / lo, lane)
-size_t rvsr_dcn_bwd6_agt_bytes(int B, int Co, int Ho, int Wo) {
-    return (size_t)B * (((Ho + 7) / 8) * 8) * ((Wo + 31) / 32) * (size_t)(2 * ((Co + 63) / 64)) * 4 * 64 * 16;
-}
-
-// The geometries dcn_bwdw6 takes: dcn_bwdin6's (which writes its gOut operand), at most 256 units, and 32-bit byte offsets into the 64
-// gOut planes of a unit.  Every other call takes dcn_bwdw2 / dcn_bwdw4.
-bool rvsr_dcn_bwdw6_takes(const DcnGeom& d) {
-    return rvsr_dcn_bwdin6_takes(d) && bwdw6_streams(d.Co, d.C, 1, nullptr, nullptr) > 0 &&
-           (size_t)64 * d.Ho * d.Wo * sizeof(float) < ((size_t)1 << 31);
-}
-
 template <int R, int TH>
-static int launch_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb, void* workspace, int ns, int nmb, int xcd, hipStream_t st) {
-    constexpr int TR = TH + 2 * R + 3, TC = 32 + 2 * R + 3, NPOS = TR * TC;
-    const size_t lds = (size_t)NPOS * 32 + (size_t)2 * TH * 8 * 64 * 16;
+static int launch_bwdw6(const DcnGeom& d, const DcnBwdPlan& q, const void* agt, float* part, float* bpart, hipStream_t st) {
     DcnBwdW6Params p;
-    p.d = d; p.agt = (const bf16x8*)agt; p.agt_nmb32 = 2 * nmb; p.agt_rows = ((d.Ho + 7) / 8) * 8;
-    const size_t nw = (size_t)d.Co * d.C * 9;
-    p.part = (float*)workspace;
-    p.bpart = gb ? p.part + (size_t)ns * nw : nullptr;
-    p.ns = ns; p.nty = (d.Ho + TH - 1) / TH; p.ntiles = d.B * p.nty * d.ntx; p.nmb = nmb; p.xcd_map = xcd;
-    const int nt = rvsr_gemm_terms();
-    auto k = nt == 2 ? dcn_bwdw6_kernel<R, 2, TH> : (nt == 1 ? dcn_bwdw6_kernel<R, 1, TH> : dcn_bwdw6_kernel<R, 3, TH>);
-    if (set_lds(k, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwdw6: cannot reserve %zu B of LDS", lds);
-    const int U = (d.C / 8) * nmb;
-    hipLaunchKernelGGL(k, dim3(ns * U), dim3(TH * 64), lds, st, p);
+    p.d = d; p.agt = (const bf16x8*)agt; p.agt_nmb32 = 2 * q.nmb; p.agt_rows = ((d.Ho + 7) / 8) * 8;
+    p.part = part; p.bpart = bpart;
+    p.ns = q.ns; p.nty = (d.Ho + TH - 1) / TH; p.ntiles = d.B * p.nty * d.ntx; p.nmb = q.nmb; p.xcd_map = q.xcd;
+    auto k = q.w_nt == 2 ? dcn_bwdw6_kernel<R, 2, TH> : (q.w_nt == 1 ? dcn_bwdw6_kernel<R, 1, TH> : dcn_bwdw6_kernel<R, 3, TH>);
+    if (set_lds(k, q.w_lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwdw6: cannot reserve %zu B of LDS", q.w_lds);
+    hipLaunchKernelGGL(k, dim3(q.P * q.gy), dim3(TH * 64), q.w_lds, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn_bwdw6 launch: %s", hipGetErrorString(e));
-    rvsr_launch_reduce(p.part, ns, nw, gw, 1, st, p.bpart, (size_t)d.Co, gb);
     return RVSR_OK;
 }
-
-// gw / gb are ACCUMULATED into (the reference's convention, cpp:659-671).  RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdw4.
-int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (!rvsr_dcn_bwdw6_takes(d) || agt == nullptr) return RVSR_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < rvsr_dcn_bwdw6_workspace_bytes(d.Co, d.C)) return RVSR_ERR_UNSUPPORTED;
-    int nmb = 0, xcd = 0;
-    const int wpc = bwdw6_wpc();
-    const int ns = bwdw6_streams(d.Co, d.C, wpc, &nmb, &xcd);
-    if (wpc == 2) return launch_bwdw6<2, 4>(d, agt, gw, gb, workspace, ns, nmb, xcd, st);
-    return launch_bwdw6<4, 8>(d, agt, gw, gb, workspace, ns, nmb, xcd, st);
+int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const DcnBwdPlan& q, const void* agt, float* part, float* bpart, hipStream_t st) {
+    if (q.w_th == 4) return launch_bwdw6<2, 4>(d, q, agt, part, bpart, st);
+    return launch_bwdw6<4, 8>(d, q, agt, part, bpart, st);
 }

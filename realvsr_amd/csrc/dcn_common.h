@@ -1,10 +1,13 @@
-// dcn_common.h -- geometry / sampling helpers shared by dcn_kernels.hip (f32 MFMA) and dcn2_kernels.hip (bf16x3).
+// dcn_common.h -- what every DCN translation unit shares (dcn_kernels.hip, dcn2_kernels.hip, dcn3_kernels.hip, dcn6_kernels.hip): the
+// geometry and parameter blocks of the kernels, the sampling rule, the device-side halo selection, and the launchers' declarations.
+// Which kernels a call runs is decided in dcn_plan.h.
 #pragma once
 #include "rvsr_common.h"
 
 #define DCN_CC 8      // input channels per K chunk
 #define DCN_KC 72     // = DCN_CC * 9 column rows per chunk
 #define DCN_NPX 128   // pixels per tile (4 rows x 32)
+#define D2_R 3        // halo radius (pixels) of the LDS x tile of dcn_fwd2 / dcn_bwdw2 / dcn_bwdw4 beyond the 3x3 footprint (dcn_tile.h)
 
 struct DcnGeom {
     const float* x;       // (B, C, H, W)
@@ -103,32 +106,20 @@ struct DcnFwdParams {
 };
 
 
-// bf16x3 forward (dcn2_kernels.hip); returns RVSR_ERR_UNSUPPORTED if the geometry is not covered
-size_t rvsr_dcn_fwd2_workspace_bytes(int Co, int C);
-int rvsr_launch_dcn_fwd2(const DcnFwdParams& p, void* workspace, size_t workspace_bytes, hipStream_t st, const unsigned* probe = nullptr,
-                         size_t nprobe = 0, int halo_hint = 0);
-// third-generation forward (dcn3_kernels.hip): consumes the weight image rvsr_launch_dcn_fwd2 packs; stride 1, dilation 1
-int rvsr_launch_dcn_fwd3(const DcnFwdParams& p, const void* wpack, int mt, hipStream_t st, const unsigned* probe = nullptr, size_t nprobe = 0,
-                         int halo_hint = 0);
-// the sampled offset statistic both DCN directions select their tile halo from (dcn6_kernels.hip); returns the sample count
-size_t rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st);
-int rvsr_launch_dcn_bwdw2(const DcnGeom& d, const TView& g, float* part, float* bpart_or_null, int P, int nty, int gy, int gz,
-                          hipStream_t st);
-// Sixth-generation backward (dcn6_kernels.hip).  The two predicates are the only statement of what the kernels take: the launchers, the
-// backward's dispatcher and its workspace query all go through them.
-//   rvsr_dcn_bwdin6_takes: 8 | channels per deformable group, 8 | C, stride 1, dilation 1, Co <= 128, one batch element's planes below 2 GB;
-//   rvsr_dcn_bwdw6_takes:  the same, plus at most 256 (8-channel chunk, 64 output channels) units and 64 gOut planes below 2 GB.
-bool rvsr_dcn_bwdin6_takes(const DcnGeom& d);
-bool rvsr_dcn_bwdw6_takes(const DcnGeom& d);
-// input / offset / mask gradient: one shared fixed-point LDS window per workgroup, lane = (pixel, tap), packed math; halo < 0 = window chosen
-// on the device.  RVSR_ERR_UNSUPPORTED (not taken, or no workspace): the caller falls back to the first-generation dcn_bwd_input_kernel.
-size_t rvsr_dcn_bwdin6_workspace_bytes(int Co, int C);
-int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
-                           float* gmask, size_t gmask_bs, void* workspace, size_t workspace_bytes, hipStream_t st, int halo = -1,
-                           const unsigned* probe_in = nullptr, void* agt = nullptr);
-// weight / bias gradient: column values transposed by the matrix core, chunk-major persistent; gw / gb accumulated into.
-// RVSR_ERR_UNSUPPORTED: the caller falls back to dcn_bwdw2 / dcn_bwdw4.
-// Its gOut operand comes pre-transposed from dcn_bwdin6 (`agt`, rvsr_dcn_bwd6_agt_bytes): the two run as a pair.
-size_t rvsr_dcn_bwdw6_workspace_bytes(int Co, int C);
-size_t rvsr_dcn_bwd6_agt_bytes(int B, int Co, int Ho, int Wo);
-int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const void* agt, float* gw, float* gb, void* workspace, size_t workspace_bytes, hipStream_t st);
+// The launchers: each takes the plan of the call (dcn_plan.h), maps its coordinates to a kernel and launches; none decides anything.
+struct DcnFwdPlan;
+struct DcnBwdPlan;
+// the sampled offset statistic both DCN directions select their tile halo from (dcn6_kernels.hip); `cnt`: zeroed by the caller
+void rvsr_launch_dcn_offset_probe(const DcnGeom& d, unsigned* cnt, hipStream_t st);
+// forward (dcn2_kernels.hip, dcn3_kernels.hip): the weight image of dcn_fwd2 / dcn_fwd3 into `wpack`, then one of the two families
+void rvsr_launch_dcn_fwd_pack(const DcnFwdParams& p, void* wpack, hipStream_t st);
+int rvsr_launch_dcn_fwd2(const DcnFwdParams& p, const DcnFwdPlan& q, const void* wpack, hipStream_t st);
+int rvsr_launch_dcn_fwd3(const DcnFwdParams& p, const DcnFwdPlan& q, const void* wpack, const unsigned* probe, hipStream_t st);
+// input / offset / mask gradient (dcn6_kernels.hip): one shared fixed-point LDS window per workgroup, lane = (pixel, tap), packed math; its
+// weight image, column norms and counters live at the start of `workspace` (bwdin6_workspace); `probe`: the caller's counters or nullptr
+int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const DcnBwdPlan& q, const float* weight, const TView& g, float* gx, float* goff, size_t goff_bs,
+                           float* gmask, size_t gmask_bs, void* workspace, const unsigned* probe, hipStream_t st);
+// weight / bias gradient partials into `part` / `bpart` (nullable): dcn_bwdw6 (dcn6_kernels.hip; column values transposed by the matrix core,
+// chunk-major persistent, its gOut operand pre-transposed by dcn_bwdin6 at `agt`), dcn_bwdw4 / dcn_bwdw2 (dcn2_kernels.hip)
+int rvsr_launch_dcn_bwdw6(const DcnGeom& d, const DcnBwdPlan& q, const void* agt, float* part, float* bpart, hipStream_t st);
+int rvsr_launch_dcn_bwdw2(const DcnGeom& d, const DcnBwdPlan& q, const TView& g, float* part, float* bpart, hipStream_t st);

@@ -23,7 +23,7 @@
 
 #include <string.h>
 
-#include "dcn_common.h"
+#include "dcn_plan.h"
 
 // Build the column tile of channel chunk [c0, c0+8) for the 128 pixels of a tile.
 // COLT == false: col[k * 128 + px]      (k-major; B operand of the forward GEMM)
@@ -358,190 +358,128 @@ __global__ __launch_bounds__(RVSR_WG, 1) void dcn_bwd_weight_kernel(const DcnBwd
 // host side
 
 
+// The developer switches of dcn_plan.h, read once.
+const DcnSwitches& rvsr_dcn_switches() {
+    static const DcnSwitches sw = [] {
+        DcnSwitches s = {};
+        const char* e = getenv("RVSR_DCN_BWD");
+        s.bwd_pair = !e || !strcmp(e, "7") ? 1 : (!strcmp(e, "64") ? 0 : -1);
+        snprintf(s.bwd_text, sizeof(s.bwd_text), "%s", e ? e : "");
+        e = getenv("RVSR_DCN5_HALO");
+        s.bwdin6_halo = e ? atoi(e) : -1;
+        e = getenv("RVSR_DCN3_HALO");
+        s.fwd3_halo = e ? atoi(e) : -1;
+        e = getenv("RVSR_BWDW6_WG");
+        s.bwdw6_wpc = e && atoi(e) == 2 ? 2 : 1;
+        return s;
+    }();
+    return sw;
+}
+
 static int fill_geom(DcnGeom& d, const float* x, const float* offset, size_t off_bs, const float* mask, size_t mask_bs,
                      int mask_logit, int B, int C, int H, int W, int Co, int kh, int kw, int stride_h, int stride_w,
                      int pad_h, int pad_w, int dil_h, int dil_w, int group, int dg, const char** why) {
-    if (!x || !offset || !mask || B <= 0 || C <= 0 || Co <= 0 || H <= 0 || W <= 0) { *why = "null/empty argument"; return RVSR_ERR_BAD_ARG; }
-    if (kh != 3 || kw != 3) { *why = "only 3x3 kernels are implemented on the HIP path"; return RVSR_ERR_UNSUPPORTED; }
-    if (group != 1) { *why = "only group == 1 is implemented on the HIP path"; return RVSR_ERR_UNSUPPORTED; }
-    if (stride_h != stride_w || pad_h != pad_w || dil_h != dil_w) { *why = "anisotropic stride/pad/dilation"; return RVSR_ERR_UNSUPPORTED; }
-    if (dg <= 0 || C % dg) { *why = "channels not divisible by deformable_group"; return RVSR_ERR_BAD_ARG; }
-    const int cpg = C / dg;
-    if (!(cpg % DCN_CC == 0 || DCN_CC % cpg == 0)) { *why = "channels per deformable group must divide or be a multiple of 8"; return RVSR_ERR_UNSUPPORTED; }
+    if (!x || !offset || !mask) { *why = "null/empty argument"; return RVSR_ERR_BAD_ARG; }
+    const DcnRefusal t = dcn_fused_takes(B, C, H, W, Co, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, group, dg);
+    if (t.rc) { *why = t.msg; return t.rc; }
     d.x = x; d.offset = offset; d.mask = mask; d.off_bs = off_bs; d.mask_bs = mask_bs; d.mask_logit = mask_logit;
     d.B = B; d.C = C; d.H = H; d.W = W; d.Co = Co;
-    d.stride = stride_h; d.pad = pad_h; d.dil = dil_h; d.dg = dg; d.cpg = cpg;
+    d.stride = stride_h; d.pad = pad_h; d.dil = dil_h; d.dg = dg; d.cpg = C / dg;
     d.Ho = (H + 2 * pad_h - (dil_h * 2 + 1)) / stride_h + 1;
     d.Wo = (W + 2 * pad_w - (dil_w * 2 + 1)) / stride_w + 1;
-    if (d.Ho <= 0 || d.Wo <= 0) { *why = "empty output"; return RVSR_ERR_BAD_ARG; }
     d.ntx = (d.Wo + 31) / 32;
     d.swz = rvsr_swizzle_enabled();
     return RVSR_OK;
 }
 
+template <int MT, int CHS>
+static int launch_dcn_fwd1(const DcnFwdParams& p, const DcnFwdPlan& q, hipStream_t st) {
+    if (set_lds(dcn_fwd_kernel<MT, CHS>, q.lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd: cannot reserve %zu B of LDS", q.lds);
+    hipLaunchKernelGGL((dcn_fwd_kernel<MT, CHS>), dim3(q.gx, q.gy, q.gz), dim3(RVSR_WG), q.lds, st, p);
+    return RVSR_OK;
+}
+
+static DcnFwdPlan dcn_forward_plan(const DcnGeom& d, const void* workspace, size_t workspace_bytes, int prepacked, const void* probe, int halo_hint) {
+    return dcn_fwd_plan(d, rvsr_gemm_mode_now(), workspace != nullptr, workspace_bytes, prepacked != 0, (((uintptr_t)d.x) & 15) == 0, probe != nullptr,
+                        halo_hint, rvsr_dcn_switches());
+}
+// plan (dcn_plan.h), refuse or launch in order: probe pass, weight pack, the family's kernel(s)
 static int dcn_forward_impl(DcnGeom& d, const float* weight, const float* bias, float* out, int act, float slope,
                             void* workspace, size_t workspace_bytes, hipStream_t st, int prepacked = 0, unsigned* probe = nullptr, int halo_hint = 0) {
+    const DcnFwdPlan q = dcn_forward_plan(d, workspace, workspace_bytes, prepacked, probe, halo_hint);
+    if (q.rc) FAIL(q.rc, "%s", q.msg);
     DcnFwdParams p;
     p.d = d; p.w = weight; p.bias = bias; p.out = out; p.act = act & 0xff; p.slope = slope; p.prepacked = prepacked;
     p.sel = dcn_halo_always();
-    if (rvsr_gemm_mode_now() != 1 && workspace != nullptr) {  // bf16x3 second-generation kernel
-        // `probe`: three zeroed device counters; filled with the offset statistic that selects the tile halo on the device (and that
-        // the backward of the same layer reuses)
-        size_t nprobe = 0;
-        if (probe != nullptr && d.cpg % 8 == 0 && d.stride == 1 && d.dil == 1) nprobe = rvsr_launch_dcn_offset_probe(d, probe, st);
-        const int rc = rvsr_launch_dcn_fwd2(p, workspace, workspace_bytes, st, nprobe ? probe : nullptr, nprobe, halo_hint);
-        if (rc != RVSR_ERR_UNSUPPORTED) return rc;
+    if (q.probe_pass) rvsr_launch_dcn_offset_probe(d, probe, st);
+    if (q.pack) rvsr_launch_dcn_fwd_pack(p, workspace, st);
+    if (q.family == DCN_FWD3) return rvsr_launch_dcn_fwd3(p, q, workspace, probe, st);
+    if (q.family == DCN_FWD2) return rvsr_launch_dcn_fwd2(p, q, workspace, st);
+    int rc = RVSR_OK;
+    switch (q.mt * 10 + q.chs) {
+        case 18: rc = launch_dcn_fwd1<1, 8>(p, q, st); break;
+        case 10: rc = launch_dcn_fwd1<1, 0>(p, q, st); break;
+        case 28: rc = launch_dcn_fwd1<2, 8>(p, q, st); break;
+        case 20: rc = launch_dcn_fwd1<2, 0>(p, q, st); break;
+        case 48: rc = launch_dcn_fwd1<4, 8>(p, q, st); break;
+        default: rc = launch_dcn_fwd1<4, 0>(p, q, st); break;
     }
-    const int nty = (d.Ho + 3) / 4;
-    const bool c8 = d.cpg % DCN_CC == 0;  // every chunk of 8 channels shares one offset set
-#define LAUNCH_FWD(MT)                                                                                              \
-    do {                                                                                                            \
-        const size_t lds = sizeof(float) * (DCN_KC * DCN_NPX + DCN_KC * (MT * 32 + 1));                             \
-        const dim3 grid(d.ntx * nty, (d.Co + MT * 32 - 1) / (MT * 32), d.B);                                        \
-        if (c8) {                                                                                                   \
-            if (set_lds(dcn_fwd_kernel<MT, 8>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd: cannot reserve %zu B of LDS", lds); \
-            hipLaunchKernelGGL((dcn_fwd_kernel<MT, 8>), grid, dim3(RVSR_WG), lds, st, p);                           \
-        } else {                                                                                                    \
-            if (set_lds(dcn_fwd_kernel<MT, 0>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd: cannot reserve %zu B of LDS", lds); \
-            hipLaunchKernelGGL((dcn_fwd_kernel<MT, 0>), grid, dim3(RVSR_WG), lds, st, p);                           \
-        }                                                                                                           \
-    } while (0)
-    if (d.Co <= 32)
-        LAUNCH_FWD(1);
-    else if (d.Co <= 64)
-        LAUNCH_FWD(2);
-    else
-        LAUNCH_FWD(4);
-#undef LAUNCH_FWD
+    if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn_fwd launch: %s", hipGetErrorString(e));
     return RVSR_OK;
 }
 
-static int bww_P(int ntiles, int gy, int gz) {
-    int P = 256 / (gy * gz);
-    if (P < 1) P = 1;
-    if (P > ntiles) P = ntiles;
-    return P;
-}
-
 extern "C" size_t rvsr_modulated_deform_conv_forward_workspace_bytes(int channels, int channels_out) {
-    return rvsr_dcn_fwd2_workspace_bytes(channels_out, channels);
-}
-
-// everything but the operand buffer dcn_bwdin6 hands to dcn_bwdw6 (that buffer sits behind it, 256-byte aligned)
-static size_t dcn_backward_workspace_base(int batch, int channels, int height, int width, int channels_out, int stride, int pad, int dil) {
-    const int Ho = (height + 2 * pad - (dil * 2 + 1)) / stride + 1, Wo = (width + 2 * pad - (dil * 2 + 1)) / stride + 1;
-    const int ntiles = batch * ((Ho + 3) / 4) * ((Wo + 31) / 32);
-    const int gy = (channels_out + 63) / 64, gz = (channels + DCN_CC - 1) / DCN_CC;
-    const size_t Q = 8 * (size_t)bww_P(ntiles, gy, gz);
-    const size_t a = sizeof(float) * Q * ((size_t)channels_out * channels * 9 + channels_out);
-    const size_t b6 = rvsr_dcn_bwdin6_workspace_bytes(channels_out, channels);   // weight image + column norms + the probe counters
-    const size_t w6 = rvsr_dcn_bwdw6_workspace_bytes(channels_out, channels);
-    const size_t m = a > b6 ? (a > w6 ? a : w6) : (b6 > w6 ? b6 : w6);
-    return (m + 255) & ~(size_t)255;
-}
-// Bytes of the gOut^T hand-off of the dcn_bwdin6 / dcn_bwdw6 pair behind that base (hi + lo bf16 copy of gOut, 8-row x 32-column tiles: ~575 MiB
-// at B = 40, Co = 64, 180 x 320); 0: none.  The workspace query has no deformable_groups argument, so it asks rvsr_dcn_bwdw6_takes about the
-// call with the MOST offset planes a batch element can have, one deformable group per 8 channels: an upper bound of the planes, hence a buffer
-// only where dcn_bwdw6 takes the call whatever its grouping.  The backward offers the buffer where this is non-zero AND the call itself is taken.
-static size_t dcn_bwd6_handoff_bytes(int batch, int channels, int height, int width, int channels_out, int stride, int pad, int dil) {
-    DcnGeom d = {};
-    d.B = batch; d.C = channels; d.H = height; d.W = width; d.Co = channels_out; d.stride = stride; d.pad = pad; d.dil = dil;
-    d.Ho = (height + 2 * pad - (dil * 2 + 1)) / stride + 1; d.Wo = (width + 2 * pad - (dil * 2 + 1)) / stride + 1;
-    d.cpg = 8; d.dg = channels / 8;
-    return rvsr_dcn_bwdw6_takes(d) ? rvsr_dcn_bwd6_agt_bytes(batch, channels_out, d.Ho, d.Wo) : 0;
+    return dcn_fwd2_image_bytes(channels_out, channels);
 }
 extern "C" size_t rvsr_modulated_deform_conv_backward_workspace_bytes(int batch, int channels, int height, int width,
                                                                       int channels_out, int stride, int pad, int dil) {
-    return dcn_backward_workspace_base(batch, channels, height, width, channels_out, stride, pad, dil) +
-           dcn_bwd6_handoff_bytes(batch, channels, height, width, channels_out, stride, pad, dil);
+    return dcn_bwd_workspace(batch, channels, height, width, channels_out, stride, pad, dil).total;
 }
 
-// RVSR_DCN_BWD (developer A/B switch, read once): unset or 7 = dcn_bwdin6 + dcn_bwdw6 (1), 64 = dcn_bwdin6 + dcn_bwdw4 (0); anything else is
-// refused (-1) rather than ignored
-static int dcn_bwd_pair_switch() {
-    static const int v = [] {
-        const char* e = getenv("RVSR_DCN_BWD");
-        return !e || !strcmp(e, "7") ? 1 : (!strcmp(e, "64") ? 0 : -1);
-    }();
-    return v;
+static DcnBwdPlan dcn_backward_plan(const DcnGeom& d, const float* gout, const float* gact, const float* gx, const float* goff, const float* gmask,
+                                    const float* gw, const void* workspace, size_t workspace_bytes, const void* probe) {
+    return dcn_bwd_plan(d, rvsr_gemm_mode_now(), gx != nullptr, goff != nullptr, gmask != nullptr, gw != nullptr, workspace != nullptr,
+                        workspace_bytes, ((((uintptr_t)gout) | ((uintptr_t)gact)) & 15) == 0, 0, probe != nullptr, rvsr_dcn_switches());
 }
-
+// plan (dcn_plan.h), refuse or launch in order: input / offset / mask gradient, weight-gradient partials, their reduction
 static int dcn_backward_impl(DcnGeom& d, const float* weight, const float* gout, const float* gact, float gact_slope,
                              float* gx, float* goff, size_t goff_bs, float* gmask, size_t gmask_bs, float* gw, float* gb,
                              void* workspace, size_t workspace_bytes, hipStream_t st, const unsigned* probe = nullptr) {
-    const size_t need = rvsr_modulated_deform_conv_backward_workspace_bytes(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil);
-    if (gw && (!workspace || workspace_bytes < need)) FAIL(RVSR_ERR_WORKSPACE, "dcn backward: workspace %zu B < %zu B", workspace_bytes, need);
+    const DcnBwdPlan q = dcn_backward_plan(d, gout, gact, gx, goff, gmask, gw, workspace, workspace_bytes, probe);
+    if (q.rc) FAIL(q.rc, "%s", q.msg);
     TView g;
     g.p = gout; g.act = gact; g.slope = gact_slope; g.C = d.Co; g.Hs = g.Hv = d.Ho; g.Ws = g.Wv = d.Wo; g.mode = 0;
     const int nty = (d.Ho + 3) / 4;
-    const int pair = dcn_bwd_pair_switch();
-    if (pair < 0)
-        FAIL(RVSR_ERR_BAD_ARG, "dcn backward: RVSR_DCN_BWD=%.16s is not accepted: 7 (or unset) = dcn_bwdin6 + dcn_bwdw6, 64 = dcn_bwdin6 + dcn_bwdw4; "
-             "6 selected dcn_bwdin5, which was removed", getenv("RVSR_DCN_BWD"));
-    // ---- input / offset / mask gradient: dcn_bwdin6, else the first-generation kernel.  dcn_bwdin6 + dcn_bwdw6 run as a pair: the first leaves
-    // gOut (x act') behind as the matrix-core operands of the second, where the second will take the call
-    void* agt = nullptr;
-    if (gx || goff || gmask) {
-        if (!gx || !goff || !gmask) FAIL(RVSR_ERR_BAD_ARG, "dcn backward: grad_input/grad_offset/grad_mask must be given together");
-        int rc2 = RVSR_ERR_UNSUPPORTED;
-        if (rvsr_gemm_mode_now() != 1) {
-            static const int halo = [] { const char* e = getenv("RVSR_DCN5_HALO"); return e ? atoi(e) : -1; }();   // dcn_bwdin6's window; -1: selected on the device
-            if (gw && pair == 1 && rvsr_dcn_bwdw6_takes(d) && dcn_bwd6_handoff_bytes(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil))
-                agt = (unsigned char*)workspace + dcn_backward_workspace_base(d.B, d.C, d.H, d.W, d.Co, d.stride, d.pad, d.dil);
-            rc2 = rvsr_launch_dcn_bwdin6(d, weight, g, gx, goff, goff_bs, gmask, gmask_bs, workspace, workspace_bytes, st, halo, probe, agt);
-            if (rc2 != RVSR_OK) agt = nullptr;   // not written
-        }
-        if (rc2 != RVSR_ERR_UNSUPPORTED && rc2 != RVSR_OK) return rc2;
+    if (q.in_family == DCN_BWDIN6) {
+        const int rc = rvsr_launch_dcn_bwdin6(d, q, weight, g, gx, goff, goff_bs, gmask, gmask_bs, workspace, probe, st);
+        if (rc) return rc;
+    } else if (q.in_family == DCN_BWDIN1) {
         DcnBwdInParams p;
         p.d = d; p.w = weight; p.g = g; p.gx = gx; p.goff = goff; p.gmask = gmask; p.goff_bs = goff_bs; p.gmask_bs = gmask_bs;
-        const int CoP = (d.Co + 1) & ~1;
-        const size_t lds = sizeof(float) * ((size_t)CoP * DCN_NPX + (size_t)CoP * DCN_KC + DCN_KC * DCN_NPX + DCN_CC * 14 * 42);
-        // (the LDS bound belongs to the first-generation kernel only: checked where that kernel is actually launched)
-        if (rc2 != RVSR_OK && lds > 160 * 1024) FAIL(RVSR_ERR_UNSUPPORTED, "dcn backward: channels_out %d needs %zu B of LDS", d.Co, lds);
-        if (rc2 == RVSR_OK) {
-            // done by dcn_bwdin6
-        } else if (d.cpg % DCN_CC == 0) {
-            if (set_lds(dcn_bwd_input_kernel<8>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_input: cannot reserve %zu B of LDS", lds);
-            hipLaunchKernelGGL(dcn_bwd_input_kernel<8>, dim3(d.ntx * nty, 1, d.B), dim3(RVSR_WG), lds, st, p);
-        } else {
-            if (set_lds(dcn_bwd_input_kernel<0>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_input: cannot reserve %zu B of LDS", lds);
-            hipLaunchKernelGGL(dcn_bwd_input_kernel<0>, dim3(d.ntx * nty, 1, d.B), dim3(RVSR_WG), lds, st, p);
-        }
+        auto k = q.chs == 8 ? dcn_bwd_input_kernel<8> : dcn_bwd_input_kernel<0>;
+        if (set_lds(k, q.in_lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_input: cannot reserve %zu B of LDS", q.in_lds);
+        hipLaunchKernelGGL(k, dim3(d.ntx * nty, 1, d.B), dim3(RVSR_WG), q.in_lds, st, p);
     }
-    // ---- weight / bias gradient: dcn_bwdw6 if the hand-off was written, else dcn_bwdw2 / dcn_bwdw4, else the first-generation kernel
-    if (gw && agt) {
-        const int rc6 = rvsr_launch_dcn_bwdw6(d, agt, gw, gb, workspace, workspace_bytes, st);
-        if (rc6 == RVSR_OK) gw = nullptr;   // done
-        else if (rc6 != RVSR_ERR_UNSUPPORTED) return rc6;
-    }
-    if (gw) {
-        DcnBwdWParams p;
-        p.d = d; p.g = g; p.nty = nty;
-        const int gy = (d.Co + 63) / 64, gz = (d.C + DCN_CC - 1) / DCN_CC;
-        p.P = bww_P(d.B * nty * d.ntx, gy, gz);
-        size_t Q = 4 * (size_t)p.P;
+    if (q.w_family != DCN_BWDW_NONE) {
         const size_t nw = (size_t)d.Co * d.C * 9;
-        p.part = (float*)workspace;
-        int q2 = -1;
-        if (d.cpg % DCN_CC == 0) {  // second-generation builder (LDS x tile, 8 waves): 8P partials
-            float* bp2 = gb ? p.part + (size_t)8 * p.P * nw : nullptr;
-            q2 = rvsr_launch_dcn_bwdw2(d, g, p.part, bp2, p.P, nty, gy, gz, st);
-            if (q2 == -2) FAIL(RVSR_ERR_LAUNCH, "dcn_bwdw2: cannot reserve LDS");
-            if (q2 > 0) {
-                Q = (size_t)q2;
-                p.bpart = bp2;
-            }
+        float* part = (float*)workspace;
+        float* bpart = gb ? part + (size_t)q.Q * nw : nullptr;
+        int rc = RVSR_OK;
+        if (q.w_family == DCN_BWDW6) {
+            rc = rvsr_launch_dcn_bwdw6(d, q, (const unsigned char*)workspace + q.handoff_off, part, bpart, st);
+        } else if (q.w_family != DCN_BWDW1) {
+            rc = rvsr_launch_dcn_bwdw2(d, q, g, part, bpart, st);
+        } else {
+            DcnBwdWParams p;
+            p.d = d; p.g = g; p.nty = nty; p.P = q.P; p.part = part; p.bpart = bpart;
+            if (set_lds(dcn_bwd_weight_kernel<0>, q.w_lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_weight: cannot reserve %zu B of LDS", q.w_lds);
+            hipLaunchKernelGGL(dcn_bwd_weight_kernel<0>, dim3(q.P, q.gy, q.gz), dim3(RVSR_WG), q.w_lds, st, p);
         }
-        if (q2 <= 0) {
-            p.bpart = gb ? p.part + Q * nw : nullptr;
-            const size_t lds = sizeof(float) * (DCN_NPX * 65 + DCN_NPX * 97);
-            if (set_lds(dcn_bwd_weight_kernel<0>, lds)) FAIL(RVSR_ERR_LAUNCH, "dcn_bwd_weight: cannot reserve %zu B of LDS", lds);
-            hipLaunchKernelGGL(dcn_bwd_weight_kernel<0>, dim3(p.P, gy, gz), dim3(RVSR_WG), lds, st, p);
-        }
+        if (rc) return rc;
         // the reference accumulates into caller-zeroed gW/gBias (cpp:659-671) -> accumulate = 1
-        rvsr_launch_reduce(p.part, (int)Q, nw, gw, 1, st, p.bpart, (size_t)d.Co, gb);
+        rvsr_launch_reduce(part, q.Q, nw, gw, 1, st, bpart, (size_t)d.Co, gb);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(RVSR_ERR_LAUNCH, "dcn backward launch: %s", hipGetErrorString(e));
@@ -669,23 +607,51 @@ extern "C" int rvsr_deform_conv_backward_parameters(const float* input, const fl
 // ---- fused ModulatedDeformConvPack core (deform_conv.py:274-292): `om` is the raw 3*dg*9-channel output of
 // conv_offset_mask; chunk/cat is pure addressing (channels [0,2*dg*9) = offsets, the rest = mask logits) and the
 // sigmoid runs in-kernel.  Optional LeakyReLU/ReLU epilogue (EDVR_arch.py:107,130). ----
+static int dcn_pack_geom(DcnGeom& d, const char* who, const float* input, const float* om, int batch, int channels, int height, int width,
+                         int channels_out, int stride, int pad, int dilation, int deformable_group) {
+    const char* why = "";
+    int rc = fill_geom(d, input, om, 0, om, 0, 1, batch, channels, height, width, channels_out, 3, 3, stride, stride, pad, pad,
+                       dilation, dilation, 1, deformable_group, &why);
+    if (rc) FAIL(rc, "%s: %s", who, why);
+    const size_t hw = (size_t)d.Ho * d.Wo;
+    d.off_bs = d.mask_bs = (size_t)27 * deformable_group * hw;
+    d.mask = om + (size_t)18 * deformable_group * hw;
+    return RVSR_OK;
+}
+// act bit 8: `workspace` already holds the packed weight image (rvsr_dcn_pack_weights), skip the per-call pack
+// act bits 10..13: halo of the forward's LDS tile chosen by the caller (3 / 7 / 11; 0 = from `probe`, or 3 px without one)
 extern "C" int rvsr_dcn_pack_forward(const float* input, const float* weight, const float* bias, const float* om,
                                      float* output, int batch, int channels, int height, int width, int channels_out,
                                      int stride, int pad, int dilation, int deformable_group, int act, float slope,
                                      void* probe, void* workspace, size_t workspace_bytes, void* stream) {
     DcnGeom d;
-    const char* why = "";
     if (!weight || !output) FAIL(RVSR_ERR_BAD_ARG, "dcn_pack_forward: null weight/output");
-    int rc = fill_geom(d, input, om, 0, om, 0, 1, batch, channels, height, width, channels_out, 3, 3, stride, stride, pad, pad,
-                       dilation, dilation, 1, deformable_group, &why);
-    if (rc) FAIL(rc, "dcn_pack_forward: %s", why);
-    const size_t hw = (size_t)d.Ho * d.Wo;
-    d.off_bs = d.mask_bs = (size_t)27 * deformable_group * hw;
-    d.mask = om + (size_t)18 * deformable_group * hw;
-    // act bit 8: `workspace` already holds the packed weight image (rvsr_dcn_pack_weights), skip the per-call pack
-    // act bits 10..13: halo of the forward's LDS tile chosen by the caller (3 / 7 / 11; 0 = from `probe`, or 3 px without one)
+    const int rc = dcn_pack_geom(d, "dcn_pack_forward", input, om, batch, channels, height, width, channels_out, stride, pad, dilation, deformable_group);
+    if (rc) return rc;
     return dcn_forward_impl(d, weight, bias, output, act, slope, workspace, workspace_bytes, (hipStream_t)stream, (act >> 8) & 1, (unsigned*)probe,
                             (act >> 10) & 15);
+}
+// The plan of that call, without a GPU: same arguments without the stream, same return code (and rvsr_last_error), nothing launched.
+extern "C" int rvsr_dcn_pack_forward_plan(const float* input, const float* weight, const float* bias, const float* om,
+                                          float* output, int batch, int channels, int height, int width, int channels_out,
+                                          int stride, int pad, int dilation, int deformable_group, int act, float slope,
+                                          void* probe, void* workspace, size_t workspace_bytes, long long* plan) {
+    (void)bias; (void)slope;
+    DcnGeom d;
+    if (!weight || !output) FAIL(RVSR_ERR_BAD_ARG, "dcn_pack_forward: null weight/output");
+    const int rc = dcn_pack_geom(d, "dcn_pack_forward", input, om, batch, channels, height, width, channels_out, stride, pad, dilation, deformable_group);
+    if (rc) return rc;
+    const DcnFwdPlan q = dcn_forward_plan(d, workspace, workspace_bytes, (act >> 8) & 1, probe, (act >> 10) & 15);
+    long long row[36] = {q.family, q.mt, q.chs, q.nt, q.pack, q.probe_pass, (long long)q.nprobe, q.ncand};
+    for (int k = 0; k < 3; ++k) {
+        const DcnHaloCand& c = q.cand[k];
+        const long long cr[8] = {c.halo, c.ge, c.lt, c.ge2, c.thr_ge, c.thr_lt, c.thr_ge2, (long long)c.lds};
+        for (int i = 0; i < 8; ++i) row[8 + 8 * k + i] = k < q.ncand ? cr[i] : 0;
+    }
+    row[32] = q.gx; row[33] = q.gy; row[34] = q.gz; row[35] = (long long)q.lds;
+    for (int i = 0; plan && i < 36; ++i) plan[i] = row[i];
+    if (q.rc) FAIL(q.rc, "%s", q.msg);
+    return RVSR_OK;
 }
 
 // The sampled offset statistic on its own (8 zeroed uint32 on the device, 6 used): lets a caller keep the counters, e.g. to choose the
@@ -707,15 +673,49 @@ extern "C" int rvsr_dcn_pack_backward(const float* input, const float* weight, c
                                       int channels_out, int stride, int pad, int dilation, int deformable_group,
                                       const void* probe, void* workspace, size_t workspace_bytes, void* stream) {
     DcnGeom d;
-    const char* why = "";
     if (!weight || !grad_output) FAIL(RVSR_ERR_BAD_ARG, "dcn_pack_backward: null weight/grad_output");
-    int rc = fill_geom(d, input, om, 0, om, 0, 1, batch, channels, height, width, channels_out, 3, 3, stride, stride, pad, pad,
-                       dilation, dilation, 1, deformable_group, &why);
-    if (rc) FAIL(rc, "dcn_pack_backward: %s", why);
-    const size_t hw = (size_t)d.Ho * d.Wo;
-    d.off_bs = d.mask_bs = (size_t)27 * deformable_group * hw;
-    d.mask = om + (size_t)18 * deformable_group * hw;
+    const int rc = dcn_pack_geom(d, "dcn_pack_backward", input, om, batch, channels, height, width, channels_out, stride, pad, dilation, deformable_group);
+    if (rc) return rc;
     return dcn_backward_impl(d, weight, grad_output, act_out, act_slope, grad_input, grad_om, d.off_bs,
-                             grad_om ? grad_om + (size_t)18 * deformable_group * hw : nullptr, d.off_bs, grad_weight, grad_bias,
+                             grad_om ? grad_om + (size_t)18 * deformable_group * d.Ho * d.Wo : nullptr, d.off_bs, grad_weight, grad_bias,
                              workspace, workspace_bytes, (hipStream_t)stream, (const unsigned*)probe);
+}
+extern "C" int rvsr_dcn_pack_backward_plan(const float* input, const float* weight, const float* om, const float* grad_output,
+                                           const float* act_out, float act_slope, float* grad_input, float* grad_weight,
+                                           float* grad_bias, float* grad_om, int batch, int channels, int height, int width,
+                                           int channels_out, int stride, int pad, int dilation, int deformable_group,
+                                           const void* probe, void* workspace, size_t workspace_bytes, long long* plan) {
+    (void)act_slope; (void)grad_bias;
+    DcnGeom d;
+    if (!weight || !grad_output) FAIL(RVSR_ERR_BAD_ARG, "dcn_pack_backward: null weight/grad_output");
+    const int rc = dcn_pack_geom(d, "dcn_pack_backward", input, om, batch, channels, height, width, channels_out, stride, pad, dilation, deformable_group);
+    if (rc) return rc;
+    const DcnBwdPlan q = dcn_backward_plan(d, grad_output, act_out, grad_input, grad_om, grad_om, grad_weight, workspace, workspace_bytes, probe);
+    long long row[41] = {q.in_family, q.nk, q.in_nt, q.chs, (long long)q.in_lds, q.own_probe, q.ncand};
+    for (int k = 0; k < 5; ++k) {
+        const DcnHaloCand& c = q.cand[k];
+        const long long cr[4] = {c.halo, c.ge, c.lt, c.thr_lt};
+        for (int i = 0; i < 4; ++i) row[7 + 4 * k + i] = k < q.ncand ? cr[i] : 0;
+    }
+    const long long tail[14] = {q.handoff, (long long)q.handoff_off, q.w_family, q.w_r, q.w_th, q.w_nt, q.ns, q.nmb, q.xcd, q.P, q.Q, q.gy, q.gz,
+                                (long long)q.w_lds};
+    for (int i = 0; i < 14; ++i) row[27 + i] = tail[i];
+    for (int i = 0; plan && i < 41; ++i) plan[i] = row[i];
+    if (q.rc) FAIL(q.rc, "%s", q.msg);
+    return RVSR_OK;
+}
+
+// The three rules of dcn_plan.h the Python glue needs (no GPU needed): whether the fused kernels take a geometry (RVSR_OK, or the code
+// the entries return), the sample count behind the counters of rvsr_dcn_offset_probe, and the tile halo a forward with `channels_out`
+// output channels selects on the device from such counters (`counters`: HOST memory, 6 used; 0: no samples).
+extern "C" int rvsr_dcn_fused_takes(int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w, int stride_h,
+                                    int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int group, int deformable_group) {
+    return dcn_fused_takes(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+                           group, deformable_group).rc;
+}
+extern "C" size_t rvsr_dcn_probe_samples(int batch, int deformable_group, int height_out, int width_out) {
+    return dcn_probe_samples(batch, deformable_group, height_out, width_out);
+}
+extern "C" int rvsr_dcn_forward_halo(const unsigned* counters, size_t nsamples, int channels_out) {
+    return counters ? dcn_fwd3_halo_of_counters(counters, nsamples, channels_out) : 0;
 }

@@ -3,8 +3,6 @@
 #include "bf16x3.h"
 #include "dcn_common.h"
 
-#define D2_R 3  // halo radius (pixels) of the LDS x tile beyond the 3x3 footprint
-
 // Stage the x tile of NQ channel quads (channels c0 .. c0+4*NQ-1) into LDS as [quad][row][col] float4.
 // All global loads are unconditional (addresses clamped into the tensor, validity applied afterwards) and are
 // issued in batches before any LDS write: a load inside a divergent `if` is waited for at the join, which turns

@@ -263,4 +263,5 @@ __device__ __forceinline__ void buf_atomic_add(__amdgpu_buffer_rsrc_t rs, unsign
 extern int rvsr_g_gemm_mode;                 // process-wide default (rvsr_set_gemm_mode)
 extern thread_local int rvsr_t_gemm_mode;    // the calling host thread's choice (rvsr_set_gemm_mode_thread), -1 = the default
 static inline int rvsr_gemm_mode_now() { return rvsr_t_gemm_mode >= 0 ? rvsr_t_gemm_mode : rvsr_g_gemm_mode; }
-static inline int rvsr_gemm_terms() { const int m = rvsr_gemm_mode_now(); return m == 2 ? 2 : (m == 3 ? 1 : 3); }
+static inline int rvsr_gemm_terms_of(int mode) { return mode == 2 ? 2 : (mode == 3 ? 1 : 3); }   // bf16 products per f32 product
+static inline int rvsr_gemm_terms() { return rvsr_gemm_terms_of(rvsr_gemm_mode_now()); }

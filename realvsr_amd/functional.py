@@ -463,16 +463,11 @@ def _pair2(v):
 
 
 def _dcn_fused_ok(input, weight, stride, padding, dilation, groups, dg):
-    """Whether the fused f32 kernels cover this call: 3 x 3, isotropic geometry, one group, channels per deformable group a multiple or a
-    divisor of 8 (dcn_kernels.hip fill_geom)."""
+    """Whether the fused f32 kernels cover this call: f32, and a geometry they take (dcn_fused_takes, csrc/dcn_plan.h)."""
     (sh, sw), (ph, pw), (dh, dw) = _pair2(stride), _pair2(padding), _pair2(dilation)
-    C = input.shape[1]
-    if input.dtype != torch.float32 or tuple(weight.shape[2:]) != (3, 3) or sh != sw or ph != pw or dh != dw or groups != 1:
-        return False
-    if dg <= 0 or C % dg:
-        return False
-    cpg = C // dg
-    return cpg % 8 == 0 or 8 % cpg == 0
+    B, C, H, W = input.shape
+    Co, _, kh, kw = weight.shape
+    return input.dtype == torch.float32 and _lib.lib().rvsr_dcn_fused_takes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg) == 0
 
 
 def _generic_geom(input, weight, stride, padding, dilation):
@@ -778,7 +773,7 @@ class _DcnPackFused(Function):
         if stride == 1 and dilation == 1 and C % (8 * dg) == 0:
             probe = torch.zeros(8, dtype=torch.int32, device=x.device)
             _lib.check(L.rvsr_dcn_offset_probe(_p(om), B, om.shape[2], om.shape[3], dg, _p(probe), _stream()), 'dcn_offset_probe')
-            dcn_offset_stats.record(weight, probe, B * dg * 18 * ((om.shape[2] + 15) // 16) * om.shape[3])
+            dcn_offset_stats.record(weight, probe, L.rvsr_dcn_probe_samples(B, dg, om.shape[2], om.shape[3]))
         _lib.check(L.rvsr_dcn_pack_backward(_p(x), _p(weight), _p(om), _p(gout), _p(act_out), gslope, _p(gx), _p(gw),
                                             _p(gb), _p(gom), B, C, H, W, Co, stride, padding, dilation, dg, _p(probe), _p(ws),
                                             ws.numel(), _stream()), 'dcn_pack_backward')

@@ -606,3 +606,196 @@ def test_conv_workspace_bytes_pinned():
     for (C1, C2, Co, B, k, s, H, W), want in pins.items():
         got = (L.rvsr_conv2d_forward_workspace_bytes(C1, C2, Co, k), L.rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, k, s, H, W))
         assert got == want, (C1, C2, Co, B, k, s, H, W, got)
+
+
+# ---- the DCN plan (csrc/dcn_plan.h) through its exported queries: no GPU, made-up addresses
+_FWD_KEYS = ('family', 'MT', 'CHS', 'NT', 'pack', 'probe', 'nprobe', 'ncand') + tuple(
+    '%s%d' % (k, i) for i in range(3) for k in ('halo', 'ge', 'lt', 'ge2', 'thr_ge', 'thr_lt', 'thr_ge2', 'lds')) + ('gx', 'gy', 'gz', 'lds')
+_BWD_KEYS = ('in_family', 'NK', 'in_NT', 'CHS', 'in_lds', 'own_probe', 'ncand') + tuple(
+    '%s%d' % (k, i) for i in range(5) for k in ('win', 'ge', 'lt', 'thr')) + ('handoff', 'handoff_off', 'w_family', 'R', 'TH', 'w_NT', 'ns', 'nmb',
+                                                                             'xcd', 'P', 'Q', 'gy', 'gz', 'w_lds')
+DCN_FWD3, DCN_FWD2, DCN_FWD1 = 0, 1, 2
+BWDIN6, BWDIN1, BWDW6, BWDW4, BWDW2, BWDW1 = 1, 2, 1, 2, 3, 4
+
+
+def _dcn_fwd_plan(C=64, Co=64, H=45, W=80, *, B=2, dg=8, stride=1, pad=1, dil=1, probe=False, hint=0, prepacked=False, ws=0, x_off=0, gemm=None):
+    """(rc, message, plan row) of rvsr_dcn_pack_forward_plan; ws: workspace bytes relative to the query's (None: no workspace)."""
+    import ctypes
+    from realvsr_amd import _lib
+    L = _lib.lib()
+    p = lambda off, on=True: ctypes.c_void_p(_A + off) if on else None   # noqa: E731
+    row = (ctypes.c_longlong * 36)(*([-7] * 36))
+    need = L.rvsr_modulated_deform_conv_forward_workspace_bytes(C, Co)
+    L.rvsr_set_gemm_mode_thread(-1 if gemm is None else gemm)
+    try:
+        rc = L.rvsr_dcn_pack_forward_plan(p(0x100000 + x_off), p(0x200000), p(0x300000), p(0x400000), p(0x500000), B, C, H, W, Co, stride, pad, dil,
+                                          dg, 2 | (0x100 if prepacked else 0) | (hint << 10), 0.1, p(0x600000, probe), p(0x700000, ws is not None),
+                                          0 if ws is None else need + ws, row)
+    finally:
+        L.rvsr_set_gemm_mode_thread(-1)
+    return rc, L.rvsr_last_error().decode(), dict(zip(_FWD_KEYS, row))
+
+
+def _dcn_bwd_plan(C=64, Co=64, H=45, W=80, *, B=2, dg=8, stride=1, pad=1, dil=1, probe=False, gx=True, gom=True, gw=True, ws=0, g_off=0, gemm=None):
+    import ctypes
+    from realvsr_amd import _lib
+    L = _lib.lib()
+    p = lambda off, on=True: ctypes.c_void_p(_A + off) if on else None   # noqa: E731
+    row = (ctypes.c_longlong * 41)(*([-7] * 41))
+    need = L.rvsr_modulated_deform_conv_backward_workspace_bytes(B, C, H, W, Co, stride, pad, dil)
+    L.rvsr_set_gemm_mode_thread(-1 if gemm is None else gemm)
+    try:
+        rc = L.rvsr_dcn_pack_backward_plan(p(0x100000), p(0x200000), p(0x400000), p(0x500000 + g_off), None, 0.1, p(0x800000, gx), p(0x900000, gw),
+                                           p(0xa00000, gw), p(0xb00000, gom), B, C, H, W, Co, stride, pad, dil, dg, p(0x600000, probe),
+                                           p(0x40000000, ws is not None), 0 if ws is None else need + ws, row)
+    finally:
+        L.rvsr_set_gemm_mode_thread(-1)
+    return rc, L.rvsr_last_error().decode(), dict(zip(_BWD_KEYS, row))
+
+
+# Expected rows, worked out by hand from the dispatcher these plans replaced (dcn_forward_impl / dcn_backward_impl of dcn_kernels.hip,
+# rvsr_launch_dcn_fwd2 / rvsr_launch_dcn_bwdw2, rvsr_launch_dcn_fwd3, rvsr_launch_dcn_bwdin6 / rvsr_launch_dcn_bwdw6 before the plan
+# existed); B = 2, 64 -> 64 channels, 8 deformable groups, 45 x 80, pad 1 unless stated.  Counters: 2 * 144 planes * 3 rows * 80 = 69120
+# samples; 8 % + 1 = 5530, 1 % + 1 = 692, 2 % + 1 = 1383.
+_NOSEL = dict(ge0=-1, lt0=-1, ge20=-1)
+_DCN_FWD_ROWS = [
+    (dict(), dict(family=DCN_FWD3, MT=2, NT=3, pack=1, probe=0, nprobe=0, ncand=1, halo0=3, gx=18, gy=1, gz=2, lds=78080, **_NOSEL)),
+    (dict(hint=7), dict(family=DCN_FWD3, MT=2, ncand=1, halo0=7, lds=110848, **_NOSEL)),
+    (dict(hint=11), dict(family=DCN_FWD3, MT=2, ncand=1, halo0=11, lds=151808, **_NOSEL)),
+    (dict(Co=128, hint=11), dict(family=DCN_FWD3, MT=4, ncand=1, halo0=7, gy=1, lds=147968, **_NOSEL)),
+    (dict(hint=11, x_off=4), dict(family=DCN_FWD3, ncand=1, halo0=3)),           # (the 7 / 11 px tiles stage 16-byte vectors)
+    (dict(probe=True), dict(family=DCN_FWD3, MT=2, probe=1, nprobe=69120, ncand=3,
+                            halo0=3, ge0=-1, lt0=1, ge20=-1, thr_lt0=5530, lds0=78080,
+                            halo1=7, ge1=1, lt1=3, ge21=-1, thr_ge1=5530, thr_lt1=692, lds1=110848,
+                            halo2=11, ge2=3, lt2=-1, ge22=1, thr_ge2=692, thr_ge22=5530, lds2=151808)),
+    (dict(Co=128, probe=True), dict(family=DCN_FWD3, MT=4, probe=1, ncand=2, halo0=3, ge0=-1, lt0=1, thr_lt0=5530,
+                                    halo1=7, ge1=1, lt1=-1, ge21=-1, thr_ge1=5530, halo2=0)),
+    (dict(W=30, probe=True), dict(family=DCN_FWD3, probe=1, nprobe=25920, ncand=1, halo0=3, gx=6, **_NOSEL)),
+    (dict(stride=2, probe=True), dict(family=DCN_FWD2, MT=2, NT=3, pack=1, probe=0, gx=6, gy=1, gz=2, lds=78080)),
+    (dict(dil=2, probe=True), dict(family=DCN_FWD2, MT=2, probe=0, gx=18, lds=78080)),
+    (dict(C=32, probe=True), dict(family=DCN_FWD1, MT=2, CHS=0, NT=3, pack=0, probe=0, gx=36, gy=1, gz=2, lds=55584)),
+    (dict(gemm=1, probe=True), dict(family=DCN_FWD1, MT=2, CHS=8, pack=0, probe=0, gx=36, lds=55584)),
+    (dict(gemm=2), dict(family=DCN_FWD3, MT=2, NT=2)), (dict(gemm=3), dict(family=DCN_FWD3, MT=2, NT=1)),
+    (dict(Co=128, gemm=2), dict(family=DCN_FWD3, MT=4, NT=2)), (dict(Co=128, gemm=3), dict(family=DCN_FWD3, MT=4, NT=1)),
+    (dict(Co=32, gemm=2), dict(family=DCN_FWD3, MT=1, NT=3)), (dict(Co=32, gemm=3), dict(family=DCN_FWD3, MT=1, NT=3)),
+    (dict(stride=2, gemm=3), dict(family=DCN_FWD2, NT=3)),
+    (dict(ws=None, probe=True), dict(family=DCN_FWD1, MT=2, CHS=8, pack=0, probe=0)),
+    (dict(prepacked=True), dict(family=DCN_FWD3, pack=0)),
+    (dict(Co=130), dict(family=DCN_FWD3, MT=4, gy=2)),
+]
+_WINDOWS5 = dict(ncand=5, win0=2, ge0=-1, lt0=0, win1=4, ge1=0, lt1=1, win2=5, ge2=1, lt2=2, win3=8, ge3=2, lt3=4, win4=12, ge4=4, lt4=-1,
+                 thr0=1383, thr1=1383, thr2=1383, thr3=1383)
+_DCN_BWD_ROWS = [
+    (dict(), dict(in_family=BWDIN6, NK=4, in_NT=3, own_probe=1, handoff=1, handoff_off=37814272, w_family=BWDW6, R=4, TH=8, w_NT=3, ns=32, nmb=1,
+                  xcd=1, P=32, Q=32, gy=8, w_lds=157216, **_WINDOWS5)),
+    (dict(probe=True), dict(in_family=BWDIN6, own_probe=0, w_family=BWDW6, **_WINDOWS5)),
+    (dict(Co=128), dict(in_family=BWDIN6, NK=8, ncand=4, win0=2, ge0=-1, lt0=0, win1=4, ge1=0, lt1=1, win2=5, ge2=1, lt2=2, win3=8, ge3=2, lt3=-1,
+                        win4=0, handoff=1, w_family=BWDW6, ns=16, nmb=2, xcd=1, Q=16, gy=16)),
+    (dict(gemm=2), dict(in_family=BWDIN6, in_NT=2, w_family=BWDW6, w_NT=2)), (dict(Co=32, gemm=3), dict(in_family=BWDIN6, NK=2, in_NT=3, w_NT=1)),
+    (dict(gx=False, gom=False), dict(in_family=0, handoff=0, w_family=BWDW4, w_NT=3, P=32, Q=256, gy=1, gz=8, w_lds=102400)),
+    (dict(gx=False, gom=False, gemm=3), dict(w_family=BWDW4, w_NT=1)),
+    (dict(gx=False, gom=False, W=30), dict(w_family=BWDW2, P=24, Q=192, gy=1, gz=8, w_lds=98304)),
+    (dict(gx=False, gom=False, g_off=4), dict(w_family=BWDW2, P=32, Q=256)),
+    (dict(gx=False, gom=False, stride=2), dict(w_family=BWDW2)),
+    (dict(gw=False, ws=None), dict(in_family=BWDIN1, CHS=8, in_lds=106880, w_family=0)),       # (dcn_bwdin6 has no workspace)
+    (dict(gw=False), dict(in_family=BWDIN6, handoff=0, w_family=0)),
+    (dict(C=32), dict(in_family=BWDIN1, CHS=0, in_lds=106880, handoff=0, w_family=BWDW1, P=64, Q=256, gy=1, gz=4, w_lds=82944)),
+    (dict(gemm=1), dict(in_family=BWDIN1, CHS=8, in_lds=106880, handoff=0, w_family=BWDW2, P=32, Q=256)),
+    (dict(Co=130), dict(in_family=BWDIN1, CHS=8, in_lds=159680, handoff=0, w_family=BWDW4, P=10, Q=80, gy=3, gz=8)),
+    (dict(C=2056, dg=257), dict(in_family=BWDIN6, NK=4, handoff=0, w_family=BWDW4, P=1, Q=8, gy=1, gz=257)),
+    (dict(stride=2), dict(in_family=BWDIN1, CHS=8, handoff=0, w_family=BWDW2)),
+]
+
+
+def test_dcn_forward_plan_rows():
+    """Which kernels a rvsr_dcn_pack_forward call launches: one row per family and per coordinate that can differ."""
+    for call, want in _DCN_FWD_ROWS:
+        rc, _, row = _dcn_fwd_plan(**call)
+        assert rc == 0, call
+        assert {key: row[key] for key in want} == want, (call, row)
+    # a workspace one byte short, where a bf16 kernel would take the call: refused, and nothing is launched -- no probe pass, no pack
+    rc, msg, row = _dcn_fwd_plan(ws=-1, probe=True)
+    assert rc == 4 and msg == 'dcn forward: workspace 147455 B < 147456 B', (rc, msg)
+    assert (row['family'], row['probe'], row['pack'], row['ncand']) == (-1, 0, 0, 0), row
+    assert _dcn_fwd_plan(C=32, ws=-1)[0] == 0                                # (the first-generation kernel reads no weight image)
+    rc, msg, row = _dcn_fwd_plan(C=24)
+    assert rc == 1 and 'multiple of 8' in msg and row['family'] == -7        # (a call that is not valid has no plan: the row is untouched)
+
+
+def test_dcn_backward_plan_rows():
+    """Which kernels a rvsr_dcn_pack_backward call launches, and the refusals with their texts."""
+    for call, want in _DCN_BWD_ROWS:
+        rc, _, row = _dcn_bwd_plan(**call)
+        assert rc == 0, call
+        assert {key: row[key] for key in want} == want, (call, row)
+    rc, msg, row = _dcn_bwd_plan(Co=136)
+    assert rc == 1 and msg == 'dcn backward: channels_out 136 needs 164480 B of LDS' and row['in_family'] == -1, (rc, msg)
+    rc, msg, _ = _dcn_bwd_plan(gom=False)
+    assert rc == 2 and msg == 'dcn backward: grad_input/grad_offset/grad_mask must be given together', (rc, msg)
+    rc, msg, row = _dcn_bwd_plan(ws=-1)
+    assert rc == 4 and msg == 'dcn backward: workspace 40173567 B < 40173568 B' and row['w_family'] == -1, (rc, msg)
+    assert _dcn_bwd_plan(ws=None)[0] == 4 and _dcn_bwd_plan(gw=False, ws=-1)[0] == 0
+
+
+def test_dcn_workspace_bytes_pinned():
+    """The three DCN workspace queries: values of the library before dcn_bwd_workspace (dcn_plan.h) gave the layout once."""
+    from realvsr_amd import _lib
+    L = _lib.lib()
+    pins = {   # (B, C, H, W, Co, stride, pad, dil, dg of the DCNv1 query): (forward, backward, DCNv1 bytes)
+        (40, 64, 180, 320, 64, 1, 1, 1, 8): (147456, 640745472, 1967849472),
+        (8, 64, 45, 80, 128, 1, 1, 1, 8): (294912, 56688640, 73277440),
+        (1, 2056, 45, 80, 64, 1, 1, 1, 8): (4755456, 37898240, 39971840),    # 257 units: no hand-off
+        (8, 64, 45, 80, 64, 2, 1, 1, 8): (147456, 37814272, 42053632),
+        (1, 16, 7, 9, 33, 1, 1, 1, 1): (36864, 4965632, 4970240),
+        (2, 32, 9, 33, 72, 1, 2, 2, 1): (147456, 7990272, 8033280),
+        (2, 128, 45, 80, 128, 1, 1, 1, 8): (589824, 42500096, 46647296),
+        (1, 16, 8, 32, 16, 1, 1, 1, 1): (18432, 2441472, 2459904),
+    }
+    for (B, C, H, W, Co, s, p, d, dg), want in pins.items():
+        got = (L.rvsr_modulated_deform_conv_forward_workspace_bytes(C, Co), L.rvsr_modulated_deform_conv_backward_workspace_bytes(B, C, H, W, Co, s, p, d),
+               L.rvsr_deform_conv_workspace_bytes(B, C, H, W, Co, 3, 3, s, p, d, dg))
+        assert got == want, (B, C, H, W, Co, s, p, d, got)
+
+
+def test_dcn_forward_halo_is_the_device_rule(monkeypatch):
+    """rvsr_dcn_forward_halo (the host's choice from copied counters) against the thresholds the forward plan hands to the device, at,
+    just below and just above both ties (100 c1 == 8 n, 100 c3 == n): equal everywhere; DcnOffsetStats.forward_halo returns it."""
+    import ctypes
+    import types
+    from realvsr_amd import _lib, caches
+    L = _lib.lib()
+
+    class HostSlot:   # a ring slot without pinned memory and a GPU event: record() and forward_halo() run as they do on the GPU
+        def __init__(self):
+            self.counters, self.nsamples, self.tick = torch.zeros(8, dtype=torch.int32), 0, -1
+            self.event = types.SimpleNamespace(record=lambda: None, synchronize=lambda: None)
+    monkeypatch.setattr(caches, '_Slot', HostSlot)
+    n = L.rvsr_dcn_probe_samples(1, 8, 16, 100)
+    assert n == 8 * 18 * 100 == 14400 and L.rvsr_dcn_probe_samples(2, 8, 45, 80) == 69120
+    for Co in (64, 128):
+        rc, _, row = _dcn_fwd_plan(Co=Co, H=16, W=100, B=1, probe=True)
+        assert rc == 0 and row['nprobe'] == n and row['ncand'] == (3 if Co == 64 else 2)
+        assert (row['thr_lt0'], row['thr_ge1']) == (1153, 1153) and (Co == 128 or (row['thr_lt1'], row['thr_ge2'], row['thr_ge22']) == (145, 145, 1153))
+        for c1 in (1151, 1152, 1153):
+            for c3 in (143, 144, 145):
+                cnt = (ctypes.c_uint * 8)(c1 + 7, c1, c3 + 5, c3, c3, 0, 0, 0)
+                runs = [row['halo%d' % k] for k in range(row['ncand'])   # dcn_halo_not_selected with the plan's candidates
+                        if not any(row['%s%d' % (key, k)] >= 0 and cmp(cnt[row['%s%d' % (key, k)]], row['thr_%s%d' % (key, k)])
+                                   for key, cmp in (('ge', int.__lt__), ('ge2', int.__lt__), ('lt', int.__ge__)))]
+                want = 3 if c1 <= 1152 else (7 if c3 <= 144 or Co == 128 else 11)   # ties go the device's way: 100 c <= 8 n, 100 c <= n
+                assert runs == [want], (Co, c1, c3, runs)
+                assert L.rvsr_dcn_forward_halo(ctypes.cast(cnt, ctypes.c_void_p), n, Co) == want, (Co, c1, c3)
+                stats, w = caches.DcnOffsetStats(), torch.zeros(1)
+                stats.record(w, torch.tensor(list(cnt), dtype=torch.int32), n)
+                assert stats.forward_halo(w, Co) == want
+    assert L.rvsr_dcn_forward_halo(ctypes.cast((ctypes.c_uint * 8)(), ctypes.c_void_p), 0, 64) == 0
+
+
+def test_dcn_fused_ok_asks_the_library():
+    from realvsr_amd import functional as RF
+    x, w = torch.zeros(1, 16, 8, 32), torch.zeros(16, 16, 3, 3)
+    assert RF._dcn_fused_ok(x, w, 1, 1, 1, 1, 2) and RF._dcn_fused_ok(x, w, (2, 2), 1, 1, 1, 4) and RF._dcn_fused_ok(x, w, 1, 1, 1, 1, 16)
+    assert not RF._dcn_fused_ok(x.double(), w.double(), 1, 1, 1, 1, 2) and not RF._dcn_fused_ok(x, w, (1, 2), 1, 1, 1, 2)
+    assert not RF._dcn_fused_ok(x, w, 1, 1, 1, 2, 2) and not RF._dcn_fused_ok(x, w, 1, 1, 1, 1, 3) and not RF._dcn_fused_ok(x, w, 1, 1, 1, 1, 0)
+    assert not RF._dcn_fused_ok(x, torch.zeros(16, 16, 5, 5), 1, 2, 1, 1, 2)
+    assert not RF._dcn_fused_ok(torch.zeros(1, 24, 8, 32), torch.zeros(16, 24, 3, 3), 1, 1, 1, 1, 2)      # 12 channels per deformable group

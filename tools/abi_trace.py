@@ -6,7 +6,7 @@ file runs on any commit.
 Every rvsr_* call is recorded in order: the entry's name, each non-pointer argument verbatim (floats by repr), each device pointer as
 None or the index of the first pointer argument of the same call with the same address (aliasing such as "the residual is the output
 buffer" is part of the record, allocator addresses are not), a host pointer as None / 'host'.  `digest` covers everything; `launches`
-leaves out the argument-only host queries (*_workspace_bytes, rvsr_get_gemm_mode, rvsr_conv2d_forward_plan), which launch nothing.
+leaves out the argument-only host queries (*_workspace_bytes, rvsr_get_gemm_mode, the *_plan exports and the three DCN rule exports), which launch nothing.
 
 usage: python tools/abi_trace.py [--dump FILE]
 """
@@ -182,7 +182,8 @@ def main():
     counts = Counter(r[0] for r in RECORD if r[0] not in ('SECTION', 'ERROR'))
     for name in sorted(counts):
         print('%6d  %s' % (counts[name], name))
-    query = lambda r: r[0].endswith('_workspace_bytes') or r[0] in ('rvsr_get_gemm_mode', 'rvsr_conv2d_forward_plan')   # noqa: E731
+    query = lambda r: r[0].endswith(('_workspace_bytes', '_plan')) or r[0] in ('rvsr_get_gemm_mode', 'rvsr_dcn_fused_takes', 'rvsr_dcn_probe_samples',   # noqa: E731
+                                                                              'rvsr_dcn_forward_halo')
     print('calls %d  digest %s' % (sum(counts.values()), hashlib.sha256(repr(RECORD).encode()).hexdigest()))
     print('launches %d  digest %s' % (sum(v for k, v in counts.items() if not query((k,))),
                                       hashlib.sha256(repr([r for r in RECORD if not query(r)]).encode()).hexdigest()))
