@@ -311,15 +311,27 @@ int rvsr_pack_weights_batched(const void* descs, int n, void* stream);
  *         g_mode 2: stored (B,Co/4,Gs_h,Gs_w) pixel-shuffled (2*Hout, 2*Wout).
  *   gact/gact_slope: fused activation derivative (stored like gout), or NULL.
  *   accumulate 0: overwrite, 1: += .  Deterministic (fixed-order reduction of partials).
- *   Nine kernel families (vector ALU for <= 4 output channels; conv_wgrad2 / conv_wgrad5 / conv_wgrad1x1 / conv_wgrad_s2 on the bf16
- *   matrix cores; an exact-f32 kernel per geometry, which also serves GEMM mode 1): conv_wgrad_plan (csrc/conv_plan.h) picks one and
- *   its slicing into partial sums; the workspace query sizes for the largest slicing any family of the geometry can ask for. */
+ *   Ten kernel families (vector ALU for <= 4 output channels; conv_wgrad2 / conv_wgrad5 / conv_wgrad1x1s / conv_wgrad1x1 /
+ *   conv_wgrad_s2 on the bf16 matrix cores; an exact-f32 kernel per geometry, which also serves GEMM mode 1): conv_wgrad_plan
+ *   (csrc/conv_plan.h) picks one and its slicing into partial sums; the workspace query sizes for the largest slicing any family of
+ *   the geometry can ask for.  A 1x1 weight gradient runs the LDS-staged conv_wgrad1x1s when gout is plain (g_mode 0), Hout * Wout is
+ *   a multiple of 4, all pointers are 16-byte aligned, one batch element of every tensor is below 2 GB and a second input starts on a
+ *   multiple of 64 channels; otherwise conv_wgrad1x1 (Hout * Wout a multiple of 8, aligned) or the exact-f32 kernel. */
 size_t rvsr_conv2d_wgrad_workspace_bytes(int C1, int C2, int Co, int B, int ksize, int stride, int Hout, int Wout);
 int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
                                 const float* gout, const float* gact, float gact_slope, int g_mode,
                                 int Gs_h, int Gs_w, float* grad_weight, float* grad_bias, int Co, int B,
                                 int ksize, int stride, int Hout, int Wout, int accumulate,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* conv_wgrad_plan's answer for that call, without running it (no GPU needed, nothing launched, no pointer dereferenced): the arguments
+ * of rvsr_conv2d_backward_weight that the plan looks at, the same validation and return code, and plan[4] = {family in the order of
+ * ConvWgradFamily (0 vector ALU, 1 conv_wgrad2, 2 conv_wgrad5, 3 exact f32 5x5, 4 conv_wgrad1x1s, 5 conv_wgrad1x1, 6 exact f32 3x3,
+ * 7 conv_wgrad_s2, 8 exact f32 3x3 stride 2, 9 exact f32 1x1), partial sums P, grid y, grid z}.  The workspace the call needs is
+ * rvsr_conv2d_wgrad_workspace_bytes >= 4 * P * (Co * (C1 + C2) * k * k + Co) bytes. */
+int rvsr_conv2d_backward_weight_plan(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
+                                     const float* gout, const float* gact, float gact_slope, int g_mode,
+                                     int Gs_h, int Gs_w, float* grad_weight, int Co, int B, int ksize, int stride,
+                                     int Hout, int Wout, int* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * 3. Fusion / resampling element-wise chain

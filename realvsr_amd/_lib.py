@@ -57,6 +57,8 @@ SIGNATURES = {
     'rvsr_conv2d_backward_weight': (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_float, c_int, c_int,
                                             c_int, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
                                             c_size, c_fp]),
+    'rvsr_conv2d_backward_weight_plan': (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_float, c_int, c_int, c_int, c_fp] +
+                                         [c_int] * 6 + [ctypes.POINTER(c_int)]),
     'rvsr_upsample_bilinear_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_int, c_float, c_fp]),
     'rvsr_upsample_bilinear_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_int, c_float, c_fp]),
     'rvsr_maxavgpool_forward': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),

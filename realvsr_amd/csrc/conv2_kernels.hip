@@ -1572,6 +1572,171 @@ int rvsr_launch_conv_wgrad1x1(const ConvWgradParams& p, int gy, int gz, hipStrea
 }
 
 // ==========================================================================================
+// The same GEMM, LDS-staged and software-pipelined in the manner of conv_wgrad2_kernel: conv_wgrad1x1s_kernel.
+// One persistent workgroup of 8 waves owns a 64(o) x 320(c) block of gW -- up to 20 32 x 32 tiles, wave (m, ng) holds the tiles
+// (m, ng), (m, ng + 4), (m, ng + 8) -- and walks its slice of the pixels once in tiles of 64: G is read once, not once per 64-channel
+// block.  A tile is fetched with coalesced 16-byte raw buffer loads (a thread's item = 8 consecutive pixels of one row, which is the K
+// order both MFMA operands want), split to bf16 hi / lo ONCE on the way to LDS and read from there by the waves that need it; the
+// loads of tile t + 1 are issued under the MFMAs of tile t, a part per k-step.  Out-of-range items (a row past Co / Ctot, pixels past
+// the image) carry a lane offset beyond the 2 GB view and load zeros: no clamps, no selects.  X item i of a thread belongs to the
+// 64-channel block i of the workgroup, so the input is picked per item: a second input has to start on a multiple of 64 channels.
+// act', the bias gradient and the deterministic partials [P][Co][Ctot] are those of conv_wgrad1x1_kernel.  Eligibility and slicing:
+// conv_plan.h (CONV_WGRAD_1X1S).
+#define WG1_THREADS 512
+#define WG1_KT 64                      // pixels per tile
+#define WG1_CB 320                     // input channels per workgroup
+#define WG1_RP 144                     // bytes per row of a tile in LDS: 64 bf16 + 16 B pad
+#define WG1_ROWS (64 + WG1_CB)         // G rows, then X rows
+template <bool ACT>
+__global__ __launch_bounds__(WG1_THREADS, 1) void conv_wgrad1x1s_kernel(const ConvWgradParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    unsigned char* t_hi = smem_raw;                      // [WG1_ROWS][WG1_RP]
+    unsigned char* t_lo = smem_raw + WG1_ROWS * WG1_RP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 31, hi = lane >> 5;
+    const int m = wave & 1, ng = wave >> 1;
+    const int C1 = p.x.a.C, C2 = p.x.b.C, Ctot = C1 + C2;
+    const int HW = p.Hout * p.Wout;
+    const int o0 = blockIdx.y * 64, c0 = blockIdx.z * WG1_CB;
+    const int cb = Ctot - c0 < WG1_CB ? Ctot - c0 : WG1_CB;   // channels of this workgroup
+    const int nblk = (cb + 63) / 64, ntile = (cb + 31) / 32;  // its 64-channel blocks (X items) and 32-channel N tiles
+    const bool m_live = o0 + m * 32 < p.Co;
+    const bool do_bias = p.bpart != nullptr && blockIdx.z == 0;
+
+    constexpr int NXI = WG1_CB / 64;
+    constexpr unsigned OOB = 0x80000000u;
+    const int q = tid & 7, r64 = tid >> 3;               // the thread's pixel octet and row (of G, and of every 64-channel block of X)
+    const unsigned g_vo = o0 + r64 < p.Co ? 4u * (unsigned)((o0 + r64) * HW + 8 * q) : OOB;
+    unsigned x_vo[NXI];
+#pragma unroll
+    for (int i = 0; i < NXI; ++i) {
+        const int c = c0 + 64 * i + r64;
+        x_vo[i] = c < Ctot ? 4u * (unsigned)((c >= C1 ? c - C1 : c) * HW + 8 * q) : OOB;
+    }
+    const size_t img_g = (size_t)p.Co * HW, img_x1 = (size_t)C1 * HW, img_x2 = (size_t)C2 * HW;
+
+    typedef float f32x4v __attribute__((ext_vector_type(4)));
+    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned vo, unsigned so) {
+        const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)so, 0));
+        return make_float4(v.x, v.y, v.z, v.w);
+    };
+    float4 gv[2], sv[ACT ? 2 : 1], xv[NXI][2];
+    float bacc = 0.f;
+
+    const int U = (HW + WG1_KT - 1) / WG1_KT;            // tiles per image
+    const int ntiles = p.B * U;
+    const int per = (ntiles + p.P - 1) / p.P;
+    const int t_begin = blockIdx.x * per, t_end = t_begin + per < ntiles ? t_begin + per : ntiles;
+
+    // part < 0: the whole tile (prologue); else one part per k-step of the MFMA phase -- 0: G (and act'), 1: X items 0, 1,
+    // 2: X items 2, 3, 3: X item 4 -- so that the requests trickle out under the matrix work (see conv_wgrad2_kernel)
+    auto issue_loads = [&](int tile, int part) {
+        int b = tile / U;
+        int px0 = (tile - b * U) * WG1_KT;
+        asm volatile("" : "+s"(b), "+s"(px0));
+        const int left = HW - px0;                       // (HW % 4 == 0: a float4 is entirely inside the image or outside)
+        const unsigned so = 4u * (unsigned)px0;
+        if (part < 0 || part == 0) {
+            const __amdgpu_buffer_rsrc_t g_rs = buf_view_2g(p.g.p + (size_t)b * img_g);
+            const __amdgpu_buffer_rsrc_t s_rs = buf_view_2g(ACT ? p.g.act + (size_t)b * img_g : p.g.p);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const unsigned vo = 8 * q + 4 * kk < left ? g_vo + 16u * kk : OOB;
+                gv[kk] = ld4(g_rs, vo, so);
+                if (ACT) sv[kk] = ld4(s_rs, vo, so);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NXI; ++i) {
+            if (part >= 0 && part != 1 + (i >> 1)) continue;
+            const bool sec = c0 + 64 * i >= C1;          // (uniform) this block's channels come from the second input
+            const float* ximg = sec ? p.x.b.p + (size_t)b * img_x2 : p.x.a.p + (size_t)b * img_x1;
+            const __amdgpu_buffer_rsrc_t x_rs = buf_view_2g(c0 + 64 * i < Ctot ? ximg : p.x.a.p);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) xv[i][kk] = ld4(x_rs, 8 * q + 4 * kk < left ? x_vo[i] + 16u * kk : OOB, so);
+        }
+    };
+    auto commit = [&]() {
+        {
+            float v[8] = {gv[0].x, gv[0].y, gv[0].z, gv[0].w, gv[1].x, gv[1].y, gv[1].z, gv[1].w};
+            if (ACT) {
+                const float s[8] = {sv[0].x, sv[0].y, sv[0].z, sv[0].w, sv[1].x, sv[1].y, sv[1].z, sv[1].w};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] *= s[j] > 0.f ? 1.f : p.g.slope;
+            }
+            bacc += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+            bf16x8 h8, l8;
+            split8(v, h8, l8);
+            *reinterpret_cast<bf16x8*>(t_hi + r64 * WG1_RP + q * 16) = h8;
+            *reinterpret_cast<bf16x8*>(t_lo + r64 * WG1_RP + q * 16) = l8;
+        }
+#pragma unroll
+        for (int i = 0; i < NXI; ++i) {
+            if (i >= nblk) continue;                     // (uniform; no wave reads the rows of a block the workgroup does not have)
+            const float v[8] = {xv[i][0].x, xv[i][0].y, xv[i][0].z, xv[i][0].w, xv[i][1].x, xv[i][1].y, xv[i][1].z, xv[i][1].w};
+            bf16x8 h8, l8;
+            split8(v, h8, l8);
+            const int dst = (64 + 64 * i + r64) * WG1_RP + q * 16;
+            *reinterpret_cast<bf16x8*>(t_hi + dst) = h8;
+            *reinterpret_cast<bf16x8*>(t_lo + dst) = l8;
+        }
+    };
+
+    f32x16 acc[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[j] = zero16();
+    if (t_begin < t_end) issue_loads(t_begin, -1);
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        const int next = tile + 1 < t_end ? tile + 1 : tile;   // (after the last tile: that tile again, nothing is committed)
+        commit();
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < WG1_KT / 16; ++ks) {
+            issue_loads(next, ks);
+            __builtin_amdgcn_sched_barrier(0);
+            if (!m_live) continue;
+            const int koff = ks * 32 + hi * 16;          // this lane's 8 pixels of the k-step
+            const int goff = (m * 32 + lo) * WG1_RP + koff;
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(t_hi + goff), al = *reinterpret_cast<const bf16x8*>(t_lo + goff);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int nt = ng + 4 * j;
+                if (nt >= ntile) continue;               // (wave-uniform)
+                const int xoff = (64 + nt * 32 + lo) * WG1_RP + koff;
+                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(t_hi + xoff), bl = *reinterpret_cast<const bf16x8*>(t_lo + xoff);
+                acc[j] = mfma_bf16(ah, bh, acc[j]);
+                acc[j] = mfma_bf16(ah, bl, acc[j]);
+                acc[j] = mfma_bf16(al, bh, acc[j]);
+            }
+        }
+        __syncthreads();
+    }
+
+    float* part = p.part + (size_t)blockIdx.x * p.Co * Ctot;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int nt = ng + 4 * j, c = c0 + nt * 32 + lo;
+        if (!m_live || nt >= ntile || c >= Ctot) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = o0 + m * 32 + drow(r, hi);
+            if (o < p.Co) part[(size_t)o * Ctot + c] = acc[j][r];
+        }
+    }
+    if (do_bias) {   // the 8 lanes of a row hold its eight octets; a row past Co loaded zeros
+        float v = bacc;
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 4);
+        if (q == 0 && o0 + r64 < p.Co) p.bpart[(size_t)blockIdx.x * p.Co + o0 + r64] = v;
+    }
+}
+
+int rvsr_launch_conv_wgrad1x1s(const ConvWgradParams& p, int gy, int gz, hipStream_t st) {
+    auto k = p.g.act != nullptr ? conv_wgrad1x1s_kernel<true> : conv_wgrad1x1s_kernel<false>;
+    return rvsr_conv_launch("conv_wgrad1x1s", k, dim3(p.P, gy, gz), WG1_THREADS, (size_t)2 * WG1_ROWS * WG1_RP, st, p);
+}
+
+// ==========================================================================================
 // Weight gradient of a 3x3 STRIDE-2 convolution (pad 1) on the bf16 matrix cores, direct from global memory like
 // conv_wgrad1x1_kernel:   gW[o][c][dy][dx] = sum_{b, py, px} G[o][py][px] * X[c][2 py + dy - 1][2 px + dx - 1].
 // K = output pixels; lane (row, k-octet) holds 8 consecutive output pixels of one output row.  For X that is a

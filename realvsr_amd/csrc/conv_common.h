@@ -100,6 +100,7 @@ size_t rvsr_conv_fwd2_workspace_bytes(int ksize, int Co, int Ctot);
 int rvsr_launch_conv_fwd2(ConvFwdParams p, const ConvFwdPlan& q, int ksize, int stride, void* workspace, size_t workspace_bytes, hipStream_t st);
 int rvsr_launch_conv_wgrad2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad1x1(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
+int rvsr_launch_conv_wgrad1x1s(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad_s2(const ConvWgradParams& p, int gy, int gz, hipStream_t st);
 int rvsr_launch_conv_wgrad5(const ConvWgradParams& p, int stride, int gy, int gz, hipStream_t st);
 // conv_thin_kernels.hip: 3x3 / stride-1 layers with <= 4 output channels on the vector ALU (exact f32)

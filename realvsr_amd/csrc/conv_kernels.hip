@@ -407,20 +407,15 @@ static int launch_wgrad(const ConvWgradParams& p, int gy, int gz, hipStream_t st
     return rvsr_conv_launch("conv_wgrad", conv_wgrad_kernel<KS, STRIDE, CCW>, dim3(p.P, gy, gz), RVSR_WG, sizeof(float) * (128 * 65 + CCW * CS), st, p);
 }
 
-extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
-                                           const float* gout, const float* gact, float gact_slope, int g_mode,
-                                           int Gs_h, int Gs_w, float* grad_weight, float* grad_bias, int Co, int B,
-                                           int ksize, int stride, int Hout, int Wout, int accumulate, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
+// Validates a weight-gradient call and fills its parameter block (without the slicing: P, part, bpart).
+static int conv_wgrad_params(ConvWgradParams& p, const float* x1, int C1, const float* x2, int C2, int Hin, int Win, const float* gout,
+                             const float* gact, float gact_slope, int g_mode, int Gs_h, int Gs_w, float* grad_weight, int Co, int B,
+                             int ksize, int stride, int Hout, int Wout) {
     if (!x1 || !gout || !grad_weight || B <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: null/empty argument");
     if ((x2 == nullptr) != (C2 == 0)) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: x2/C2 disagree");
     if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: kernel size %d", ksize);
     if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: stride %d", stride);
     if (g_mode != 0 && g_mode != 2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: gradient view mode %d", g_mode);
-    const size_t need = rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, ksize, stride, Hout, Wout);
-    if (!workspace || workspace_bytes < need)
-        FAIL(RVSR_ERR_WORKSPACE, "conv2d_backward_weight: workspace %zu B < %zu B", workspace_bytes, need);
-    ConvWgradParams p;
     make_view(p.x.a, x1, nullptr, 0.f, C1, Hin, Win, 0, 0, 0);
     make_view(p.x.b, x2, nullptr, 0.f, C2, Hin, Win, 0, 0, 0);
     if (make_view(p.g, gout, gact, gact_slope, Co, Gs_h, Gs_w, g_mode, 0, 0) || p.g.Hv != Hout || p.g.Wv != Wout)
@@ -429,13 +424,46 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
     const int pad = ksize / 2;
     if ((Hin + 2 * pad - ksize) / stride + 1 != Hout || (Win + 2 * pad - ksize) / stride + 1 != Wout)
         FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: input %dx%d does not give output %dx%d", Hin, Win, Hout, Wout);
+    p.part = p.bpart = nullptr;
     p.B = B;
     p.Co = Co;
     p.Hout = Hout;
     p.Wout = Wout;
     p.ntx = (Wout + 31) / 32;
     p.nty = (Hout + 3) / 4;
+    p.P = 0;
     p.ring = 0;   // (the X-row ring of conv_wgrad2 measured no gain, profiles/r04_notes.md: compiled out, WGRAD2_RING in conv2_kernels.hip)
+    return RVSR_OK;
+}
+
+// The plan of a weight-gradient call, without a GPU: the arguments of rvsr_conv2d_backward_weight that the plan looks at, same
+// validation and return code, nothing launched.  plan[4] = {family (ConvWgradFamily), P, grid y, grid z}.
+extern "C" int rvsr_conv2d_backward_weight_plan(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
+                                                const float* gout, const float* gact, float gact_slope, int g_mode,
+                                                int Gs_h, int Gs_w, float* grad_weight, int Co, int B, int ksize, int stride,
+                                                int Hout, int Wout, int* plan) {
+    ConvWgradParams p;
+    const int rc = conv_wgrad_params(p, x1, C1, x2, C2, Hin, Win, gout, gact, gact_slope, g_mode, Gs_h, Gs_w, grad_weight, Co, B, ksize,
+                                     stride, Hout, Wout);
+    if (rc) return rc;
+    const ConvWgradPlan q = conv_wgrad_plan(p, ksize, stride, rvsr_gemm_mode_now());
+    const int row[4] = {q.family, q.P, q.gy, q.gz};
+    for (int i = 0; plan && i < 4; ++i) plan[i] = row[i];
+    return RVSR_OK;
+}
+
+extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
+                                           const float* gout, const float* gact, float gact_slope, int g_mode,
+                                           int Gs_h, int Gs_w, float* grad_weight, float* grad_bias, int Co, int B,
+                                           int ksize, int stride, int Hout, int Wout, int accumulate, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    ConvWgradParams p;
+    const int prc = conv_wgrad_params(p, x1, C1, x2, C2, Hin, Win, gout, gact, gact_slope, g_mode, Gs_h, Gs_w, grad_weight, Co, B, ksize,
+                                      stride, Hout, Wout);
+    if (prc) return prc;
+    const size_t need = rvsr_conv2d_wgrad_workspace_bytes(C1, C2, Co, B, ksize, stride, Hout, Wout);
+    if (!workspace || workspace_bytes < need)
+        FAIL(RVSR_ERR_WORKSPACE, "conv2d_backward_weight: workspace %zu B < %zu B", workspace_bytes, need);
     const ConvWgradPlan q = conv_wgrad_plan(p, ksize, stride, rvsr_gemm_mode_now());
     const size_t nw = (size_t)Co * (C1 + C2) * ksize * ksize;
     p.P = q.P;
@@ -448,6 +476,7 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
         case CONV_WGRAD2: rc = rvsr_launch_conv_wgrad2(p, q.gy, q.gz, st); break;
         case CONV_WGRAD5: rc = rvsr_launch_conv_wgrad5(p, stride, q.gy, q.gz, st); break;
         case CONV_WGRAD_F32_5: rc = stride == 1 ? launch_wgrad<5, 1, 16>(p, q.gy, q.gz, st) : launch_wgrad<5, 2, 16>(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_1X1S: rc = rvsr_launch_conv_wgrad1x1s(p, q.gy, q.gz, st); break;
         case CONV_WGRAD_1X1: rc = rvsr_launch_conv_wgrad1x1(p, q.gy, q.gz, st); break;
         case CONV_WGRAD_F32_3S1: rc = launch_wgrad<3, 1, 64>(p, q.gy, q.gz, st); break;
         case CONV_WGRAD_S2: rc = rvsr_launch_conv_wgrad_s2(p, q.gy, q.gz, st); break;

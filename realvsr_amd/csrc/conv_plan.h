@@ -178,7 +178,8 @@ enum ConvWgradFamily {
     CONV_WGRAD2,           // conv_wgrad2_kernel: 3x3 / stride 1 on the bf16 matrix cores
     CONV_WGRAD5,           // conv_wgrad5_kernel: 5x5 on the bf16 matrix cores
     CONV_WGRAD_F32_5,      // conv_wgrad_kernel<5, S, 16>: GEMM mode 1
-    CONV_WGRAD_1X1,        // conv_wgrad1x1_kernel: a plain GEMM on the bf16 matrix cores
+    CONV_WGRAD_1X1S,       // conv_wgrad1x1s_kernel: a plain GEMM on the bf16 matrix cores, LDS-staged and pipelined, 64 x 320 blocks of gW
+    CONV_WGRAD_1X1,        // conv_wgrad1x1_kernel: the same GEMM straight from global memory, 64 x 64 blocks
     CONV_WGRAD_F32_3S1,    // conv_wgrad_kernel<3, 1, 64>
     CONV_WGRAD_S2,         // conv_wgrad_s2_kernel: 3x3 / stride 2 on the bf16 matrix cores
     CONV_WGRAD_F32_3S2,    // conv_wgrad_kernel<3, 2, 32>
@@ -196,7 +197,7 @@ static inline bool conv_wgrad_can(int family, int ksize, int stride, int Co) {
         case CONV_WGRAD2: case CONV_WGRAD_F32_3S1: return ksize == 3 && stride == 1;
         case CONV_WGRAD5: case CONV_WGRAD_F32_5: return ksize == 5;
         case CONV_WGRAD_S2: case CONV_WGRAD_F32_3S2: return ksize == 3 && stride == 2;
-        default: return ksize == 1;   // CONV_WGRAD_1X1, CONV_WGRAD_F32_1
+        default: return ksize == 1;   // CONV_WGRAD_1X1S, CONV_WGRAD_1X1, CONV_WGRAD_F32_1
     }
 }
 // How a family slices the pixels into P partial sums, and its grid.
@@ -224,6 +225,16 @@ static inline ConvWgradPlan conv_wgrad_slicing(int family, int B, int Hout, int 
         case CONV_WGRAD_F32_3S2:
             gz = (Ctot + 31) / 32;
             break;
+        case CONV_WGRAD_1X1S: {   // one workgroup of 8 waves per CU and 64 x 320 block, pixels cut into 64-pixel tiles inside an image; never
+            // more partial sums than CONV_WGRAD_1X1 would write for the geometry, so the workspace query is what it was
+            const long P1 = 1024 / ((long)gy * gz);
+            gz = (Ctot + 319) / 320;
+            units = (long)B * ((Hout * Wout + 63) / 64);
+            if (units > ntiles) units = ntiles;
+            slots = 256;
+            if (P1 < slots / ((long)gy * gz)) slots = P1 * gy * gz;
+            break;
+        }
         case CONV_WGRAD_1X1: case CONV_WGRAD_F32_1:   // the GEMM kernel runs 4 small workgroups per CU and hides its load latency with occupancy
             slots = 1024;
             break;
@@ -259,6 +270,11 @@ static inline ConvWgradPlan conv_wgrad_plan(const ConvWgradParams& p, int ksize,
                 // second input has to start on a multiple of 64 channels
                 return split && p.Wout % 4 == 0 && al && conv_span_ok(p.Hout, p.Wout, p.Co > Ctot ? p.Co : Ctot) && (C2 == 0 || C1 % 64 == 0);
             case CONV_WGRAD5: return split;   // (the mode's terms, deterministic partials like the others)
+            case CONV_WGRAD_1X1S:
+                // 16-byte loads of 8-pixel items: whole float4s inside an image; one image of each tensor behind 32-bit byte offsets
+                // (raw buffers, < 2 GB); the input is picked per 64-channel block
+                return split && plain_g && (p.Hout * p.Wout) % 4 == 0 && al && (C2 == 0 || C1 % 64 == 0) &&
+                       conv_span_ok(p.Hout, p.Wout, p.Co > (C1 > C2 ? C1 : C2) ? p.Co : (C1 > C2 ? C1 : C2));
             case CONV_WGRAD_1X1: return split && plain_g && (p.Hout * p.Wout) % 8 == 0 && al;
             case CONV_WGRAD_S2: return split && C2 == 0 && plain_g && p.Wout % 8 == 0 && p.x.a.Ws % 4 == 0 && al;
             default: return true;   // the exact-f32 kernels take what is left
