@@ -55,8 +55,23 @@ def _ref(x1, x2, w, b, res, stride, act, ps):
 gemm_mode = gemm_modes()
 
 
+def _at_offset(t, off, d, leaf=True):
+    """`t` on the device, starting `off` floats behind a 16-byte boundary inside a larger flat buffer; leaf: it wants a gradient."""
+    if t is None:
+        return None
+    if off:
+        buf = torch.zeros(t.numel() + 8, device=d)
+        assert buf.data_ptr() % 16 == 0
+        v = buf[off:off + t.numel()].view(t.shape)
+        v.copy_(t)
+    else:
+        v = t.to(d)
+    return v.requires_grad_(True) if leaf else v
+
+
 @pytest.mark.parametrize('case', CASES, ids=lambda c: '-'.join(str(v) for v in c))
-def test_conv_block_forward_backward(case, gemm_mode):
+def test_conv_block_forward_backward(case, gemm_mode, offsets=(0, 0, 0, 0)):
+    """offsets: float offsets of x1, x2, the output gradient and the residual from a 16-byte boundary (tests/test_gpu_conv_ledger.py)."""
     from realvsr_amd import functional as RF
     TOL = TOLS[gemm_mode]
     C1, C2, Co, k, stride, act, use_res, ps, B, H, W = case
@@ -87,10 +102,10 @@ def test_conv_block_forward_backward(case, gemm_mode):
 
     d = dev()
     conv = conv.to(d)
-    t = [v.to(d).requires_grad_(True) if v is not None else None for v in (x1, x2, res)]
+    t = [_at_offset(v, off, d) for v, off in zip((x1, x2, res), (offsets[0], offsets[1], offsets[3]))]
     code = {'none': RF.ACT_NONE, 'relu': RF.ACT_RELU, 'lrelu': RF.ACT_LRELU}[act]
     y = RF.conv2d(t[0], conv, code, 0.1, x2=t[1], residual=t[2], pixel_shuffle=ps)
-    y.backward(gout.to(d))
+    y.backward(_at_offset(gout, offsets[2], d, leaf=False))
     torch.cuda.synchronize()
     check('out', y, yr, TOL)
     check('grad_x1', t[0].grad, r[0].grad, TOL)
@@ -204,3 +219,108 @@ def test_mask_epilogue_refused_or_exact(bf16x3_mode):
             assert rc == 0, (rc, msg)
             ref = F.conv2d(x.double(), w.double(), b.double(), padding=1) * torch.where(res.double() > 0, 1.0, 0.1)
             check('masked data gradient', out, ref, TOLS['bf16x3'])
+
+
+# ---- what only the raw C ABI reaches: an output buffer off a 16-byte boundary, act' on a strided or 5x5 forward conv, the mask epilogue
+# with act' in the speed modes.  Calls as tests/conv_ledger.py describes them (the coverage ledger, tests/test_conv_ledger_host.py,
+# takes its raw-ABI keys from RAW_LEDGER_CALLS); every tensor sits inside a larger buffer of sentinels that must stay untouched.
+def _raw_ledger_calls():
+    from conv_ledger import fwd_call
+    return [
+        ('out+res off', fwd_call(64, 64, 8, 64, 8, 64, 1, res=True, res_off=1, out_off=1)),   # W % 4 == 0: element stores by alignment alone
+        ('act s2 Co64', fwd_call(64, 64, 16, 32, 8, 16, 1, stride=2, xact=True)),
+        ('act s2 Co16', fwd_call(16, 16, 9, 30, 5, 15, 2, stride=2, xact=True)),
+        ('act 5x5', fwd_call(16, 16, 9, 30, 9, 30, 1, k=5, xact=True)),
+        ('ps view, out off', fwd_call(64, 16, 16, 32, 8, 16, 1, in_mode=2, w_mode=1, xact=True, out_off=1)),
+        ('zero-insert view, out off', fwd_call(64, 64, 8, 16, 16, 32, 1, in_mode=1, w_mode=1, out_off=1)),
+    ]
+
+
+RAW_LEDGER_CALLS = _raw_ledger_calls()
+_PAD = 32   # floats of sentinel on either side (a multiple of 4: the tensor's own offset decides its alignment)
+
+
+def _padded(t, off, d):
+    """(buffer, view): `t` at `off` floats behind a 16-byte boundary, sentinels around it."""
+    buf = torch.full((t.numel() + 2 * _PAD + 4,), SENTINEL, device=d)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[_PAD + off:_PAD + off + t.numel()].view(t.shape)
+    v.copy_(t)
+    return buf, v
+
+
+def _border_untouched(buf, off, n):
+    return bool((buf[:_PAD + off] == SENTINEL).all()) and bool((buf[_PAD + off + n:] == SENTINEL).all())
+
+
+def _raw_call(call, seed, slope=0.1):
+    """Runs one single-input, single-output rvsr_conv2d_forward call on seeded tensors; returns (code, message, output, float64
+    reference, borders untouched)."""
+    from realvsr_amd import _lib
+    from realvsr_amd._lib import _p, _stream
+    c = call
+    assert c['C2'] == 0 and c['Co2'] == 0 and not c['ps']
+    L, d = _lib.lib(), dev()
+    g = torch.Generator().manual_seed(seed)
+    B, C, Co, k, T = c['B'], c['C1'], c['Co1'], c['k'], c['k'] ** 2
+    x = torch.randn(B, C // 4 if c['in_mode'] == 2 else C, c['Hs'], c['Ws'], generator=g)
+    xact = torch.randn(x.shape, generator=g) if c['xact'] else None
+    w = torch.randn((C, Co, k, k) if c['w_mode'] & 1 else (Co, C, k, k), generator=g) / (T * C) ** 0.5
+    bias = torch.randn(Co, generator=g) * 0.1
+    res = torch.randn(B, Co, c['Hout'], c['Wout'], generator=g) if c['res'] else None
+
+    xin = x.double() if xact is None else x.double() * torch.where(xact.double() > 0, 1.0, slope)
+    if c['in_mode'] == 2:       # stored pixel-shuffled
+        xin = F.pixel_unshuffle(xin, 2)
+    elif c['in_mode'] == 1:     # the zero-insert view of a stride-2 data gradient
+        z = torch.zeros(B, C, c['Hout'], c['Wout'], dtype=torch.float64)
+        z[:, :, 0:2 * c['Hs']:2, 0:2 * c['Ws']:2] = xin
+        xin = z
+    weff = w.double().transpose(0, 1).flip(2, 3) if c['w_mode'] & 1 else w.double()
+    ref = F.conv2d(xin, weff, bias.double(), stride=c['stride'], padding=k // 2)
+    if c['act'] == 3:
+        ref = ref * torch.where(res.double() > 0, 1.0, slope)
+    else:
+        ref = F.leaky_relu(ref, slope) if c['act'] == 2 else F.relu(ref) if c['act'] == 1 else ref
+        ref = ref if res is None else ref + res.double()
+
+    xb, xv = _padded(x, c['x_off'], d)
+    ab, av = _padded(xact, c['xact_off'], d) if c['xact'] else (None, None)
+    rb, rv = _padded(res, c['res_off'], d) if c['res'] else (None, None)
+    ob, ov = _padded(torch.full(tuple(ref.shape), SENTINEL), c['out_off'], d)
+    wd, bd = w.to(d), bias.to(d)
+    ws = torch.empty(L.rvsr_conv2d_forward_workspace_bytes(C, 0, Co, k), dtype=torch.uint8, device=d)
+    rc = L.rvsr_conv2d_forward(_p(xv), C, None, 0, _p(av), slope, c['in_mode'], c['Hs'], c['Ws'], _p(wd), _p(bd), _p(rv), _p(ov), Co, None, 0, B, k,
+                               c['stride'], c['w_mode'], c['act'], slope, 0, c['Hout'], c['Wout'], _p(ws), ws.numel(), _stream())
+    torch.cuda.synchronize()
+    clean = _border_untouched(ob, c['out_off'], ov.numel()) and _border_untouched(xb, c['x_off'], xv.numel()) and \
+        (rb is None or _border_untouched(rb, c['res_off'], rv.numel())) and (ab is None or _border_untouched(ab, c['xact_off'], av.numel()))
+    return rc, (L.rvsr_last_error() or b'').decode(), ov, ref, clean
+
+
+@pytest.mark.parametrize('name,call', RAW_LEDGER_CALLS, ids=[n.replace(' ', '_') for n, _ in RAW_LEDGER_CALLS])
+def test_raw_abi_calls_vs_float64(name, call, gemm_mode):
+    rc, msg, out, ref, clean = _raw_call(call, 11)
+    assert rc == 0, (rc, msg)
+    assert clean, 'a store outside the output (or into an input)'
+    check(name, out, ref, TOLS[gemm_mode])
+
+
+@pytest.mark.parametrize('mode', ['bf16x2', 'bf16'])
+def test_mask_epilogue_with_act_in_in_the_speed_modes(mode):
+    """act 3 with act' on the input, two terms and one term per product, on a frame the 8 x 64 tile takes with a ragged last row and a
+    ragged last column tile (17 x 60)."""
+    from conv_ledger import fwd_call, fwd_plan
+    from realvsr_amd import _lib
+    call = fwd_call(64, 64, 17, 60, 17, 60, 1, w_mode=1, act=3, res=True, xact=True)
+    rc, row = fwd_plan(call, mode)
+    assert rc == 0 and (row['wide'], row['NT'], row['act_in']) == (1, 2 if mode == 'bf16x2' else 1, 1), row
+    old = _lib.get_gemm_mode()
+    _lib.set_gemm_mode(mode)
+    try:
+        rc, msg, out, ref, clean = _raw_call(call, 12)
+    finally:
+        _lib.set_gemm_mode(old)
+    assert rc == 0, (rc, msg)
+    assert clean
+    check('masked data gradient with act\', ' + mode, out, ref, TOLS[mode])

@@ -238,6 +238,23 @@ def test_conv_shapes_in_the_speed_modes(case, speed_mode):
     test_conv_block_forward_backward(case, speed_mode)
 
 
+def _speed_mode_ledger_cases():
+    """The cases of tests/test_gpu_conv_ledger.py (with their pointer offsets) that the same filter admits: the coverage ledger of the
+    forward kernels in these modes (tests/test_conv_ledger_host.py) counts them."""
+    from test_gpu_conv_ledger import LEDGER_CASES
+    return [(c, o) for c, o in LEDGER_CASES if c[3] == 3 and c[4] == 1 and c[2] > 32]
+
+
+def _ledger_id(v):
+    return '-'.join(str(x) for x in v[0]) + ('' if not any(v[1]) else '+' + ''.join(str(o) for o in v[1]))
+
+
+@pytest.mark.parametrize('case', _speed_mode_ledger_cases(), ids=_ledger_id)
+def test_ledger_shapes_in_the_speed_modes(case, speed_mode):
+    from test_gpu_conv import test_conv_block_forward_backward
+    test_conv_block_forward_backward(case[0], speed_mode, offsets=case[1])
+
+
 def _speed_mode_dcn_cases():
     from test_gpu_dcn import SHAPES, _random_shapes
     # more than 32 output channels, stride / dilation 1: dcn_fwd3<MT >= 2>, dcn_bwdin6<NK >= 4>, dcn_bwdw6 -- the kernels the modes act in
@@ -304,3 +321,9 @@ def test_conv_shapes_in_the_f16fp8_mode(case, f16fp8_mode):
     """The conv shape sweep (ragged tiles, concat inputs, residuals, PixelShuffle stores, widths on and off the vector path) in the 'f16fp8' mode."""
     from test_gpu_conv import test_conv_block_forward_backward
     test_conv_block_forward_backward(case, 'f16fp8')
+
+
+@pytest.mark.parametrize('case', _speed_mode_ledger_cases(), ids=_ledger_id)
+def test_ledger_shapes_in_the_f16fp8_mode(case, f16fp8_mode):
+    from test_gpu_conv import test_conv_block_forward_backward
+    test_conv_block_forward_backward(case[0], 'f16fp8', offsets=case[1])
