@@ -500,6 +500,39 @@ int rvsr_gan_loss_forward(const float* a, size_t na, const float* b, size_t nb, 
 int rvsr_gan_loss_backward(const float* a, size_t na, size_t nb, const float* saved, const float* gscalar, float target, float scale,
                            float* ga, float* gb, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8. Channel attention of RCAN (codes/models/archs/RCAN_arch.py:30-70: ChannelAttention, and the scaled residual add of RCAB)
+ * --------------------------------------------------------------------------------------------- */
+
+/* One fused operator on f32 NCHW contiguous tensors, C channels squeezed to Cr = C / squeeze_factor >= 1:
+ *   pooled[b,c] = mean_hw u[b,c]                                  (AdaptiveAvgPool2d(1))
+ *   hidden[b,j] = relu(w1[j,:] . pooled[b,:] + b1[j])             (w1: Cr x C, the 1x1 squeeze conv)
+ *   gate[b,c]   = sigmoid(w2[c,:] . hidden[b,:] + b2[c])          (w2: C x Cr, the 1x1 excite conv)
+ *   out         = (x ? x : 0) + res_scale * u * gate              (x NULL: no residual)
+ * pooled (B x C), hidden (B x Cr) and gate (B x C) are written out for the backward.  Two launches: plane sums (one read of u), then
+ * gate + stream (reads u and x, writes out).  No matrix cores and no atomics: exact f32 in every GEMM mode, bit-identical from run to
+ * run.  workspace: rvsr_channel_attention_workspace_bytes(B, C, H, W) bytes, forward and backward alike.
+ * Refused with RVSR_ERR_UNSUPPORTED: C > 4096 (the LDS scratch of the gate), Cr < 1 or Cr > C, a plane of 2^31 elements, null pointers. */
+size_t rvsr_channel_attention_workspace_bytes(int B, int C, int H, int W);
+/* The plan of a call without running it (pure host code, no GPU needed, no pointer dereferenced: the three streamed tensors are only
+ * tested for alignment): *slices = workgroups and partial sums per (b, c) plane -- 1 where B * C planes fill the chip, more for a few
+ * planes of a large frame; *vec = 1 when the kernels use 16-byte loads and stores (H * W % 4 == 0 and all three addresses 16-byte
+ * aligned; x may be NULL), else 0, the scalar path.  Either output pointer may be NULL. */
+int rvsr_channel_attention_plan(int B, int C, int H, int W, const void* u, const void* x, const void* out, int* slices, int* vec);
+int rvsr_channel_attention_forward(const float* u, const float* x /*NULL ok*/, const float* w1, const float* b1, const float* w2,
+                                   const float* b2, float* out, float* pooled, float* hidden, float* gate, int B, int C, int Cr, int H,
+                                   int W, float res_scale, void* ws, size_t ws_bytes, void* stream);
+/* Backward, given gout = dL/dout and the saved pooled / hidden / gate:
+ *   d[b,c] = sum_hw gout * u;  gp2 = res_scale * d * gate * (1 - gate);  gw2 = sum_b gp2 (x) hidden, gb2 = sum_b gp2;
+ *   gz = (w2^T gp2) * [hidden > 0];  gw1 = sum_b gz (x) pooled, gb1 = sum_b gz;  gs = w1^T gz / (H * W);
+ *   gu = res_scale * gate * gout + gs   (gs broadcast over the plane).
+ * The gradient of x is gout itself: the caller passes it on.  gw1 / gb1 / gw2 / gb2 are WRITTEN, not accumulated (sum over b in ascending
+ * order); any of the four may be NULL.  Three launches: plane dot products (reads gout and u), the small-matrix backward in one
+ * workgroup, the stream (reads gout, writes gu). */
+int rvsr_channel_attention_backward(const float* gout, const float* u, const float* w1, const float* w2, const float* pooled,
+                                    const float* hidden, const float* gate, float* gu, float* gw1, float* gb1, float* gw2, float* gb2,
+                                    int B, int C, int Cr, int H, int W, float res_scale, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);
  * out: workgroups x 512 floats (checksums).  MFMA work issued = workgroups * 8 waves * iters * 8 * 32768 FLOP. */

@@ -1,5 +1,7 @@
-"""define_G for the DCN-based generators (codes/models/VideoSR_archs.py:18-45: EDVR / EDVR_NoUp / TDAN branches)."""
-from .archs import EDVR_arch, TDAN_arch
+"""define_G for the generators on the MI355X path (codes/models/VideoSR_archs.py:18-58: EDVR / EDVR_NoUp / TDAN / RCAN branches)."""
+from .archs import EDVR_arch, RCAN_arch, TDAN_arch
+
+_RCAN_KEYS = ('num_in_ch', 'num_out_ch', 'num_frames', 'num_feat', 'num_group', 'num_block', 'squeeze_factor', 'res_scale')
 
 
 def define_G(opt):
@@ -14,6 +16,15 @@ def define_G(opt):
     if which_model == 'TDAN':
         return TDAN_arch.TDAN(nf=opt_net['nf'], channel=opt_net['nc'], nframes=opt_net['nframes'], nb_f=opt_net['nb_f'],
                               nb_b=opt_net['nb_b'], groups=opt_net['groups'], scale=opt['scale'])
+    if which_model == 'RCAN':
+        # A block that only names the model is not a buildable request: the reference reads every one of these keys with [] and has no
+        # defaults for them, so an incomplete block is refused like an unknown model (NotImplementedError) instead of a KeyError.
+        missing = [k for k in _RCAN_KEYS if k not in opt_net] + ([] if 'scale' in opt else ['scale (in opt)'])
+        if missing:
+            raise NotImplementedError('Generator model [RCAN]: network_G lacks ' + ', '.join(missing))
+        return RCAN_arch.RCAN(num_in_ch=opt_net['num_in_ch'], num_out_ch=opt_net['num_out_ch'], num_frames=opt_net['num_frames'],
+                              num_feat=opt_net['num_feat'], num_group=opt_net['num_group'], num_block=opt_net['num_block'],
+                              squeeze_factor=opt_net['squeeze_factor'], upscale=opt['scale'], res_scale=opt_net['res_scale'])
     raise NotImplementedError('Generator model [{:s}] not recognized'.format(which_model))
 
 

@@ -95,6 +95,10 @@ SIGNATURES = {
     'rvsr_bn_lrelu_backward': (c_int, [c_fp] * 9 + [c_int] * 4 + [c_float, c_fp, c_size, c_fp]),
     'rvsr_gan_loss_forward': (c_int, [c_fp, c_size, c_fp, c_size, c_float, c_double, c_fp, c_fp, c_fp]),
     'rvsr_gan_loss_backward': (c_int, [c_fp, c_size, c_size, c_fp, c_fp, c_float, c_float, c_fp, c_fp, c_fp]),
+    'rvsr_channel_attention_workspace_bytes': (c_size, [c_int] * 4),
+    'rvsr_channel_attention_plan': (c_int, [c_int] * 4 + [c_fp] * 3 + [ctypes.POINTER(c_int)] * 2),
+    'rvsr_channel_attention_forward': (c_int, [c_fp] * 10 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
+    'rvsr_channel_attention_backward': (c_int, [c_fp] * 12 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
     'rvsr_debug_mfma_rate': (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
 }
 

@@ -1372,6 +1372,135 @@ def gan_criterion(a, target, other=None):
     return _GANCriterion.apply(a, other, float(target))
 
 
+# ------------------------------------------------------------------------------------------ channel attention (RCAN)
+def _ca_forward(u, x, w1, b1, w2, b2, res_scale):
+    """rvsr_channel_attention_forward on contiguous tensors: (out, pooled, hidden, gate); out = (x or 0) + res_scale * u * gate."""
+    B, C, H, W = u.shape
+    Cr = w1.shape[0]
+    if tuple(w1.shape[:2]) != (Cr, C) or tuple(w2.shape[:2]) != (C, Cr) or w1.numel() != Cr * C or w2.numel() != C * Cr \
+            or b1 is None or b2 is None or b1.numel() != Cr or b2.numel() != C:
+        raise RuntimeError('channel_attention: expected biased 1x1 convs %d -> Cr -> %d, got weights %s and %s'
+                           % (C, C, tuple(w1.shape), tuple(w2.shape)))
+    if x is not None and x.shape != u.shape:
+        raise RuntimeError('channel_attention: residual %s does not match %s' % (tuple(x.shape), tuple(u.shape)))
+    out = torch.empty_like(u)
+    pooled, hidden, gate = u.new_empty(B, C), u.new_empty(B, Cr), u.new_empty(B, C)
+    L = _lib.lib()
+    ws = _workspace(L.rvsr_channel_attention_workspace_bytes(B, C, H, W), u.device)
+    _lib.check(L.rvsr_channel_attention_forward(_p(u), _p(x), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), _p(pooled), _p(hidden), _p(gate),
+                                                B, C, Cr, H, W, res_scale, _p(ws), ws.numel(), _stream()), 'channel_attention_forward')
+    return out, pooled, hidden, gate
+
+
+def _ca_backward(gout, u, w1, w2, pooled, hidden, gate, res_scale, gw1=None, gb1=None, gw2=None, gb2=None):
+    """rvsr_channel_attention_backward: gu; the parameter gradients are written into the buffers given (None: not computed)."""
+    B, C, H, W = u.shape
+    gu = torch.empty_like(u)
+    L = _lib.lib()
+    ws = _workspace(L.rvsr_channel_attention_workspace_bytes(B, C, H, W), u.device)
+    _lib.check(L.rvsr_channel_attention_backward(_p(gout), _p(u), _p(w1), _p(w2), _p(pooled), _p(hidden), _p(gate), _p(gu), _p(gw1), _p(gb1),
+                                                 _p(gw2), _p(gb2), B, C, w1.shape[0], H, W, res_scale, _p(ws), ws.numel(), _stream()),
+               'channel_attention_backward')
+    return gu
+
+
+class _ChannelAttention(Function):
+    """(x or 0) + res_scale * u * sigmoid(conv_up(relu(conv_down(mean_hw u)))) as one operator (RCAN_arch.py:30-70): four passes over the
+    tensor forward and four backward instead of the ~10 each of the composed torch ops."""
+
+    @staticmethod
+    def forward(ctx, u, x, w1, b1, w2, b2, res_scale):
+        _need_cuda(u, x, w1, b1, w2, b2)
+        u, x, w1, b1, w2, b2 = _c(u), _c(x), _c(w1), _c(b1), _c(w2), _c(b2)
+        out, pooled, hidden, gate = _ca_forward(u, x, w1, b1, w2, b2, res_scale)
+        ctx.res_scale, ctx.has_x = res_scale, x is not None
+        ctx.params = (w1, b1, w2, b2)   # only to find their gradient buffers (_pgrad)
+        ctx.save_for_backward(u, w1, w2, pooled, hidden, gate)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        u, w1, w2, pooled, hidden, gate = ctx.saved_tensors
+        gout = gout.contiguous()
+        need = ctx.needs_input_grad
+        gu = None
+        g = [None, None, None, None]
+        if need[0] or any(need[2:6]):
+            g = [_pgrad(p) if need[2 + i] else None for i, p in enumerate(ctx.params)]
+            gu = _ca_backward(gout, u, w1, w2, pooled, hidden, gate, ctx.res_scale, *g)
+        return (gu if need[0] else None), (gout if ctx.has_x and need[1] else None), g[0], g[1], g[2], g[3], None
+
+
+def channel_attention(u, conv_down, conv_up, x=None, res_scale=1.0):
+    """RCAN's ChannelAttention driven by its two 1x1 ``nn.Conv2d`` holders, with the residual add of RCAB fused:
+    out = (x or 0) + res_scale * u * sigmoid(conv_up(relu(conv_down(avg_pool(u)))))."""
+    return _ChannelAttention.apply(u, x, conv_down.weight, conv_down.bias, conv_up.weight, conv_up.bias, float(res_scale))
+
+
+class _RCABFused(Function):
+    """x + res_scale * CA(conv2(relu(conv1(x)))) as ONE autograd node (RCAB, RCAN_arch.py:51-70), built the way _ResBlockFused is: forward
+    is conv1 + ReLU, conv2, and the channel-attention operator with x as its fused residual; backward takes gu from the channel-attention
+    backward, then runs the residual block's chain on it -- conv1's data-gradient kernel adds gout as its fused residual, so the identity
+    gradient costs no pass of its own."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, wd, bd, wu, bu, res_scale):
+        _need_cuda(x, w1, b1, w2, b2, wd, bd, wu, bu)
+        x, w1, b1, w2, b2, wd, bd, wu, bu = _c(x), _c(w1), _c(b1), _c(w2), _c(b2), _c(wd), _c(bd), _c(wu), _c(bu)
+        B, C, H, W = x.shape
+        if w1.shape != (C, C, 3, 3) or w2.shape != (C, C, 3, 3):
+            raise RuntimeError('rcab: expected two %dx%dx3x3 convs' % (C, C))
+        h, u = torch.empty_like(x), torch.empty_like(x)
+        _conv(x, w1, h, bias=b1, act=ACT_RELU, what='rcab conv1')
+        _conv(h, w2, u, bias=b2, what='rcab conv2')
+        out, pooled, hidden, gate = _ca_forward(u, x, wd, bd, wu, bu, res_scale)
+        ctx.save_for_backward(x, h, u, w1, w2, wd, wu, pooled, hidden, gate)
+        ctx.res_scale = res_scale
+        ctx.has_bias = (b1 is not None, b2 is not None)
+        ctx.params = (b1, b2, wd, bd, wu, bu)   # only to find their gradient buffers (_pgrad)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, h, u, w1, w2, wd, wu, pooled, hidden, gate = ctx.saved_tensors
+        b1, b2, wd_p, bd_p, wu_p, bu_p = ctx.params
+        gout = gout.contiguous()
+        need = ctx.needs_input_grad
+        need_x, need_w1, need_b1, need_w2, need_b2 = need[:5]
+        gx = gw1 = gb1 = gw2 = gb2 = None
+        if not any(need[:9]):
+            return (None,) * 10
+        gca = [_pgrad(p) if need[5 + i] else None for i, p in enumerate((wd_p, bd_p, wu_p, bu_p))]
+        gu =_ca_backward(gout, u, wd, wu, pooled, hidden, gate, ctx.res_scale, *gca)
+        if need_w2 or need_b2:
+            gw2 = _pgrad(w2)
+            gb2 = _pgrad(b2) if ctx.has_bias[1] else None
+            _conv_wgrad(h, gu, gw2, gb2, what='rcab wgrad2')
+        if need_x or need_w1 or need_b1:
+            # as in _ResBlockFused: relu'(h) in the epilogue of conv2's data gradient where the plan grants it, else in the two consumers
+            gh = torch.empty_like(x)
+            masked = _FUSE_GRAD_MASK and _conv(gu, w2, gh, transposed=True, act=ACT_MASK, residual=h, what='rcab dgrad2')
+            if not masked:
+                _conv(gu, w2, gh, transposed=True, what='rcab dgrad2')
+            hmask = None if masked else h
+            if need_w1 or need_b1:
+                gw1 = _pgrad(w1)
+                gb1 = _pgrad(b1) if ctx.has_bias[0] else None
+                _conv_wgrad(x, gh, gw1, gb1, gact=hmask, what='rcab wgrad1')
+            if need_x:
+                gx = torch.empty_like(x)
+                _conv(gh, w1, gx, transposed=True, xact=hmask, residual=gout, what='rcab dgrad1')
+        return gx, gw1, gb1, gw2, gb2, gca[0], gca[1], gca[2], gca[3], None
+
+
+def rcab(x, conv1, conv2, conv_down, conv_up, res_scale=1.0):
+    """x + res_scale * channel_attention(conv2(relu(conv1(x)))) with the identity add fused in both directions."""
+    return _RCABFused.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias, conv_down.weight, conv_down.bias, conv_up.weight,
+                            conv_up.bias, float(res_scale))
+
+
 # ------------------------------------------------------------------------------------------ device guard
 def _guarded(fn):
     """Run an operator on the device of its tensors: HIP launches go to the CURRENT device, and `_stream()` /
