@@ -533,6 +533,52 @@ int rvsr_channel_attention_backward(const float* gout, const float* u, const flo
                                     const float* hidden, const float* gate, float* gu, float* gw1, float* gb1, float* gw2, float* gb2,
                                     int B, int C, int Cr, int H, int W, float res_scale, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 9. FSTRN: the temporal convolution of an FRB, PReLU and Dropout (codes/models/archs/FSTRN_arch.py)
+ * --------------------------------------------------------------------------------------------- */
+
+/* tconv3: nn.Conv3d(Ci, Co, (3, 1, 1), padding (1, 0, 0)) (FSTRN_arch.py:17), with the FRB's `res + out` (:22) and the PReLU of the
+ * NEXT block (:15, :21) fused, on FRAME-MAJOR f32 tensors [T, B, C, H, W], contiguous:
+ *   out[t,b,co,y,x]  = bias[co] + sum_{dt < 3, 0 <= t+dt-1 < T} sum_ci w[co,ci,dt] * s[t+dt-1,b,ci,y,x]  [+ residual[t,b,co,y,x]]
+ *   pout[t,b,co,y,x] = out > 0 ? out : slope[0] * out          (pout may be NULL; slope is a DEVICE pointer)
+ * w is the Conv3d weight, [Co, Ci, 3] contiguous.  transposed != 0: w is [Ci, Co, 3] and read as w[ci, co, 2 - dt] -- the data gradient
+ * of the convolution whose weight it is.  bias and residual may be NULL; residual may be `out` itself (in-place accumulation), s may be
+ * neither output.  One launch: a wave owns 32 pixels of a batch element and walks the frames with the operands of three frames in
+ * registers, so s is read once; the weights of all taps stay in LDS.  Products follow the calling thread's GEMM mode: three-term bf16 split,
+ * exact f32 in mode 1; modes 2 and 3 keep three terms.  No atomics: bit-identical from run to run.
+ * Refused with RVSR_ERR_UNSUPPORTED: Ci > 64 or Co > 64 (the caller composes the operator from 1x1 convolutions), a plane of 2^23
+ * elements; RVSR_ERR_BAD_ARG: empty shapes, null pointers. */
+int rvsr_tconv3_forward(const float* s, const float* w, const float* bias /*NULL ok*/, const float* residual /*NULL ok*/,
+                        const float* slope /*NULL ok without pout*/, float* out, float* pout /*NULL ok*/, int T, int B, int Ci, int Co, int H,
+                        int W, int transposed, void* stream);
+/* The plan of a call without running it (pure host code, no GPU needed, no pointer dereferenced): *vec = 1 when the kernel uses 16-byte
+ * loads and stores (H * W % 4 == 0 and s, residual, out and pout 16-byte aligned, NULL counting as aligned), else 0, the scalar path;
+ * *grid = workgroups launched.  Returns what rvsr_tconv3_forward would return for the shape.  Either output pointer may be NULL. */
+int rvsr_tconv3_plan(int T, int B, int Ci, int Co, int H, int W, const void* s, const void* residual, const void* out, const void* pout,
+                     int* vec, int* grid);
+
+/* nn.PReLU() with one learnable slope (FSTRN_arch.py:15, :42), the long skip `lr_res + out` (:60) and nn.Dropout (:43, :62) in one pass
+ * over n contiguous floats:
+ *   y = prelu(a [+ b]) [* keep * scale]        prelu(x) = x > 0 ? x : slope[0] * x;  keep: n bytes, 0 = dropped;  scale = 1 / (1 - p)
+ * b and keep may be NULL.  slope is a DEVICE pointer.  16-byte accesses when n % 4 == 0, the f32 tensors are 16-byte and keep 4-byte
+ * aligned; else scalar. */
+int rvsr_prelu_forward(const float* a, const float* b /*NULL ok*/, const float* slope, const unsigned char* keep /*NULL ok*/, float scale,
+                       float* y, size_t n, void* stream);
+/* Backward, x = a [+ b]:
+ *   gx     = g * [keep * scale] * (x > 0 ? 1 : slope[0]) [+ gres]      (gres: a gradient arriving over a skip connection; may be gx)
+ *   gslope = sum g * [keep * scale] * x * (x <= 0)                     (WRITTEN; per-workgroup partials in ws, summed by one workgroup
+ *                                                                       in an order fixed by n: bit-identical from run to run)
+ * gx or gslope may be NULL.  ws: rvsr_prelu_workspace_bytes() bytes. */
+size_t rvsr_prelu_workspace_bytes(void);
+int rvsr_prelu_backward(const float* g, const float* a, const float* b /*NULL ok*/, const float* slope, const unsigned char* keep /*NULL ok*/,
+                        float scale, const float* gres /*NULL ok*/, float* gx, float* gslope, size_t n, void* ws, size_t ws_bytes,
+                        void* stream);
+/* The plan of a PReLU call (pure host code): *vec as above for the f32 tensors of the call, f0 .. f4 (forward: a, b, y; backward: g, a, b,
+ * gres, gx; NULL where the call has none), and the keep mask; *blocks = workgroups, which is also the number of partial sums of the slope
+ * gradient.  n == 0 is RVSR_ERR_BAD_ARG. */
+int rvsr_prelu_plan(size_t n, const void* f0, const void* f1, const void* f2, const void* f3, const void* f4, const void* keep, int* vec,
+                    int* blocks);
+
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);
  * out: workgroups x 512 floats (checksums).  MFMA work issued = workgroups * 8 waves * iters * 8 * 32768 FLOP. */

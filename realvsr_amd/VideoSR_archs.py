@@ -1,6 +1,7 @@
-"""define_G for the generators on the MI355X path (codes/models/VideoSR_archs.py:18-58: EDVR / EDVR_NoUp / TDAN / RCAN branches)."""
-from .archs import EDVR_arch, RCAN_arch, TDAN_arch
+"""define_G for the generators on the MI355X path (codes/models/VideoSR_archs.py:18-58: EDVR / EDVR_NoUp / TDAN / RCAN / FSTRN branches)."""
+from .archs import EDVR_arch, FSTRN_arch, RCAN_arch, TDAN_arch
 
+_FSTRN_KEYS = ('k', 'nf', 'nframes')
 _RCAN_KEYS = ('num_in_ch', 'num_out_ch', 'num_frames', 'num_feat', 'num_group', 'num_block', 'squeeze_factor', 'res_scale')
 
 
@@ -25,6 +26,12 @@ def define_G(opt):
         return RCAN_arch.RCAN(num_in_ch=opt_net['num_in_ch'], num_out_ch=opt_net['num_out_ch'], num_frames=opt_net['num_frames'],
                               num_feat=opt_net['num_feat'], num_group=opt_net['num_group'], num_block=opt_net['num_block'],
                               squeeze_factor=opt_net['squeeze_factor'], upscale=opt['scale'], res_scale=opt_net['res_scale'])
+    if which_model == 'FSTRN':
+        # as for RCAN: the reference reads k, nf, nframes and opt['scale'] with [] and has no defaults for them
+        missing = [k for k in _FSTRN_KEYS if k not in opt_net] + ([] if 'scale' in opt else ['scale (in opt)'])
+        if missing:
+            raise NotImplementedError('Generator model [FSTRN]: network_G lacks ' + ', '.join(missing))
+        return FSTRN_arch.FSTRN(k=opt_net['k'], nf=opt_net['nf'], nframes=opt_net['nframes'], scale=opt['scale'])
     raise NotImplementedError('Generator model [{:s}] not recognized'.format(which_model))
 
 

@@ -99,6 +99,12 @@ SIGNATURES = {
     'rvsr_channel_attention_plan': (c_int, [c_int] * 4 + [c_fp] * 3 + [ctypes.POINTER(c_int)] * 2),
     'rvsr_channel_attention_forward': (c_int, [c_fp] * 10 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
     'rvsr_channel_attention_backward': (c_int, [c_fp] * 12 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
+    'rvsr_tconv3_plan': (c_int, [c_int] * 6 + [c_fp] * 4 + [ctypes.POINTER(c_int)] * 2),
+    'rvsr_tconv3_forward': (c_int, [c_fp] * 7 + [c_int] * 7 + [c_fp]),
+    'rvsr_prelu_workspace_bytes': (c_size, []),
+    'rvsr_prelu_plan': (c_int, [c_size] + [c_fp] * 6 + [ctypes.POINTER(c_int)] * 2),
+    'rvsr_prelu_forward': (c_int, [c_fp] * 4 + [c_float, c_fp, c_size, c_fp]),
+    'rvsr_prelu_backward': (c_int, [c_fp] * 5 + [c_float, c_fp, c_fp, c_fp, c_size, c_fp, c_size, c_fp]),
     'rvsr_debug_mfma_rate': (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
 }
 

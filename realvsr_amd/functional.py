@@ -1501,6 +1501,353 @@ def rcab(x, conv1, conv2, conv_down, conv_up, res_scale=1.0):
                             conv_up.bias, float(res_scale))
 
 
+# ------------------------------------------------------------------------------------------ FSTRN: frame-major 3-D convs, PReLU, FRB
+# Activations are FRAME-MAJOR, [T, B, C, H, W] contiguous: a range of frames is a contiguous batch for the [..., C, H, W] kernels above, and
+# the three temporal taps of a pixel are three pointers one frame apart (csrc/conv3d_kernels.hip).
+_FUSE_TCONV3 = True   # off: the (3,1,1) convolution composed from three 1x1 convs over frame ranges -- the fallback and the yardstick
+
+
+def _c3_taps(T, f0, f1):
+    """The temporal taps of a kernel-3 / padding-1 convolution evaluated at output frames [f0, f1) of T input frames, as
+    (dt, first input frame, frames, first output frame relative to f0).  The centre tap comes first: it covers every output frame, so
+    it WRITES the output and the outer taps accumulate onto it."""
+    taps = []
+    for dt in (1, 0, 2):
+        a, b = max(f0 + dt - 1, 0), min(f1 + dt - 1, T)
+        if b > a:
+            taps.append((dt, a, b - a, a - dt + 1 - f0))
+    return taps
+
+
+class _Conv3dFrames(Function):
+    """nn.Conv3d(Ci, Co, (3, k, k), padding (1, k // 2, k // 2)) at output frames [f0, f1) [+ residual], as accumulated 2-D convolutions
+    over frame ranges with the weight slices w[:, :, dt]; an accumulating call takes its own output buffer as the fused residual."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, f0, f1):
+        _need_cuda(x, weight, bias, residual)
+        x, weight, bias, residual = _c(x), _c(weight), _c(bias), _c(residual)
+        T, B, Ci, H, W = x.shape
+        Co, Cw, kt, k, k2 = weight.shape
+        if Cw != Ci or kt != 3 or k != k2 or not 0 <= f0 < f1 <= T:
+            raise RuntimeError('conv3d_frames: x %s, weight %s, frames [%d, %d) do not fit' % (tuple(x.shape), tuple(weight.shape), f0, f1))
+        out = x.new_empty(f1 - f0, B, Co, H, W)
+        if residual is not None and residual.shape != out.shape:
+            raise RuntimeError('conv3d_frames: residual %s does not match %s' % (tuple(residual.shape), tuple(out.shape)))
+        wdt = [weight[:, :, dt].contiguous() for dt in range(3)]
+        for i, (dt, a, n, o) in enumerate(_c3_taps(T, f0, f1)):
+            dst = out[o:o + n]
+            _conv(x[a:a + n], wdt[dt], dst, bias=bias if i == 0 else None, residual=residual if i == 0 else dst, what='conv3d_frames')
+        ctx.cfg = (f0, f1, bias is not None, residual is not None)
+        ctx.params = (weight, bias)   # only to find their gradient buffers (_pgrad)
+        ctx.save_for_backward(x, *wdt)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, *wdt = ctx.saved_tensors
+        f0, f1, has_bias, has_res = ctx.cfg
+        weight, bias = ctx.params
+        gout = gout.contiguous()
+        T = x.shape[0]
+        taps = _c3_taps(T, f0, f1)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            # the centre tap writes frames [f0, f1); frames outside that only an outer tap reaches start from zero
+            gx = torch.empty_like(x) if (f0, f1) == (0, T) else torch.zeros_like(x)
+            for i, (dt, a, n, o) in enumerate(taps):
+                dst = gx[a:a + n]
+                _conv(gout[o:o + n], wdt[dt], dst, transposed=True, residual=None if i == 0 else dst, what='conv3d_frames dgrad')
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            gw = _pgrad(weight)
+            gb = _pgrad(bias) if has_bias else None
+            tmp = torch.empty_like(wdt[0])
+            done = set()
+            for i, (dt, a, n, o) in enumerate(taps):
+                _conv_wgrad(x[a:a + n], gout[o:o + n], tmp, gb if i == 0 else None, what='conv3d_frames wgrad')
+                gw[:, :, dt].copy_(tmp)
+                done.add(dt)
+            for dt in set(range(3)) - done:   # (a tap that meets no frame: T == 1)
+                gw[:, :, dt].zero_()
+        return gx, gw, gb, (gout if has_res else None), None, None
+
+
+def conv3d_frames(x, conv3d, frames=None, residual=None):
+    """A 3 x k x k ``nn.Conv3d`` (padding 1 in time, k // 2 in space) on frame-major x [T, B, C, H, W] at the output frames
+    ``frames = (f0, f1)`` (None: all) [+ residual]: returns [f1 - f0, B, Co, H, W]."""
+    f0, f1 = (0, x.shape[0]) if frames is None else frames
+    return _Conv3dFrames.apply(x, conv3d.weight, conv3d.bias, residual, int(f0), int(f1))
+
+
+def _slope(t):
+    if t is not None and t.numel() != 1:
+        raise NotImplementedError('prelu: one slope per channel is not on the MI355X path; nn.PReLU() (one slope) is')
+    return t
+
+
+def _prelu_forward(a, b, slope, keep=None, scale=1.0):
+    """rvsr_prelu_forward: prelu(a [+ b]) [* keep * scale]; keep: a bool / uint8 tensor of a's shape."""
+    y = torch.empty_like(a)
+    _lib.check(_lib.lib().rvsr_prelu_forward(_p(a), _p(b), _p(slope), _p(keep), scale, _p(y), a.numel(), _stream()), 'prelu_forward')
+    return y
+
+
+def _prelu_backward(g, a, b, slope, keep=None, scale=1.0, gres=None, gslope=None, need_gx=True):
+    """rvsr_prelu_backward: gx = g * [keep * scale] * prelu'(a [+ b]) [+ gres]; the slope gradient is written into `gslope` (None: not
+    computed)."""
+    gx = torch.empty_like(a) if need_gx else None
+    L = _lib.lib()
+    ws = _workspace(L.rvsr_prelu_workspace_bytes(), a.device)
+    _lib.check(L.rvsr_prelu_backward(_p(g), _p(a), _p(b), _p(slope), _p(keep), scale, _p(gres), _p(gx), _p(gslope), a.numel(), _p(ws), ws.numel(),
+                                     _stream()), 'prelu_backward')
+    return gx
+
+
+def _keep_bytes(keep, like):
+    if keep is None:
+        return None
+    if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != like.shape or keep.device != like.device:
+        raise RuntimeError('prelu: keep must be a bool / uint8 tensor of shape %s on %s' % (tuple(like.shape), like.device))
+    return keep.contiguous()
+
+
+class _PReLU(Function):
+    """prelu(a [+ b]) [* keep * scale] in one pass; the gradient of a is also that of b."""
+
+    @staticmethod
+    def forward(ctx, a, b, slope, keep, scale):
+        _need_cuda(a, b, slope)
+        a, b, slope, keep = _c(a), _c(b), _c(_slope(slope)), _keep_bytes(keep, a)
+        if b is not None and b.shape != a.shape:
+            raise RuntimeError('prelu: the second addend %s does not match %s' % (tuple(b.shape), tuple(a.shape)))
+        ctx.scale, ctx.has_b, ctx.slope_p = scale, b is not None, slope
+        ctx.save_for_backward(a, b, slope, keep)
+        return _prelu_forward(a, b, slope, keep, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b, slope, keep = ctx.saved_tensors
+        need_x = ctx.needs_input_grad[0] or (ctx.has_b and ctx.needs_input_grad[1])
+        gslope = _pgrad(ctx.slope_p) if ctx.needs_input_grad[2] else None
+        gx = None
+        if need_x or gslope is not None:
+            gx = _prelu_backward(g.contiguous(), a, b, slope, keep, ctx.scale, gslope=gslope, need_gx=need_x)
+        return (gx if ctx.needs_input_grad[0] else None), (gx if ctx.has_b and ctx.needs_input_grad[1] else None), gslope, None, None
+
+
+def prelu(x, prelu_mod, b=None, keep=None, p=0.0):
+    """``nn.PReLU()`` (one learnable slope, read on the device) of x [+ b], and -- with a keep mask -- ``nn.Dropout(p)`` of the result in
+    the same pass: prelu(x + b) * keep * float32(1 / (1 - p))."""
+    scale = float(torch.tensor(1.0 / (1.0 - p), dtype=torch.float32)) if keep is not None else 1.0
+    return _PReLU.apply(x, b, prelu_mod.weight, keep, scale)
+
+
+def _tconv3_run(s, w, bias=None, residual=None, slope=None, transposed=False):
+    """out [, pout] of rvsr_tconv3_forward on frame-major s [T, B, Ci, H, W]; w: the Conv3d weight (Co, Ci, 3, 1, 1), or with `transposed`
+    the weight whose data gradient this is.  With _FUSE_TCONV3 off, or for channel counts the kernel refuses, the same result composed
+    from three accumulated 1x1 convs over frame ranges (and a PReLU pass for pout)."""
+    T, B, Ci, H, W = s.shape
+    Co = w.shape[1] if transposed else w.shape[0]
+    if w.shape[1 if not transposed else 0] != Ci or tuple(w.shape[2:]) != (3, 1, 1):
+        raise RuntimeError('tconv3: s %s and weight %s do not fit' % (tuple(s.shape), tuple(w.shape)))
+    out = s.new_empty(T, B, Co, H, W)
+    if residual is not None and residual.shape != out.shape:
+        raise RuntimeError('tconv3: residual %s does not match %s' % (tuple(residual.shape), tuple(out.shape)))
+    pout = torch.empty_like(out) if slope is not None else None
+    if _FUSE_TCONV3:
+        rc = _lib.lib().rvsr_tconv3_forward(_p(s), _p(w), _p(bias), _p(residual), _p(slope), _p(out), _p(pout), T, B, Ci, Co, H, W,
+                                            int(transposed), _stream())
+        if rc == 0:
+            return out, pout
+        if rc != 1:   # RVSR_ERR_UNSUPPORTED: channel counts the kernel does not take -- the composed path below
+            _lib.check(rc, 'tconv3')
+    for i, (dt, a, n, o) in enumerate(_c3_taps(T, 0, T)):
+        dst = out[o:o + n]
+        _conv(s[a:a + n], w[:, :, 2 - dt if transposed else dt].contiguous(), dst, bias=bias if i == 0 else None,
+              residual=residual if i == 0 else dst, transposed=transposed, what='tconv3 (composed)')
+    if pout is not None:
+        pout = _prelu_forward(out, None, slope)
+    return out, pout
+
+
+def _tconv3_wgrad(s, gout, gw, gb):
+    """Weight gradient (Co, Ci, 3, 1, 1) and bias gradient of the temporal convolution: the 1x1 weight-gradient kernel once per tap over
+    the frame range the tap meets (deterministic partial sums), scattered into the dt slices."""
+    T = s.shape[0]
+    tmp = gw.new_empty(gw.shape[0], gw.shape[1], 1, 1)
+    done = set()
+    for i, (dt, a, n, o) in enumerate(_c3_taps(T, 0, T)):
+        _conv_wgrad(s[a:a + n], gout[o:o + n], tmp, gb if i == 0 else None, what='tconv3 wgrad')
+        gw[:, :, dt].copy_(tmp)
+        done.add(dt)
+    for dt in set(range(3)) - done:
+        gw[:, :, dt].zero_()
+
+
+class _TConv3(Function):
+    """The (3,1,1) temporal convolution with bias [+ residual]; with a slope also pout = prelu(out) as a second output."""
+
+    @staticmethod
+    def forward(ctx, s, weight, bias, residual, slope):
+        _need_cuda(s, weight, bias, residual, slope)
+        s, weight, bias, residual, slope = _c(s), _c(weight), _c(bias), _c(residual), _c(_slope(slope))
+        out, pout = _tconv3_run(s, weight, bias, residual, slope)
+        ctx.cfg = (bias is not None, residual is not None, slope is not None)
+        ctx.params = (weight, bias, slope)   # only to find their gradient buffers (_pgrad)
+        ctx.save_for_backward(s, weight, slope, out if slope is not None else None)
+        if slope is None:
+            return out
+        return out, pout
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, gpout=None):
+        s, weight, slope, out = ctx.saved_tensors
+        has_bias, has_res, has_slope = ctx.cfg
+        weight_p, bias_p, slope_p = ctx.params
+        need = ctx.needs_input_grad
+        g = gout.contiguous()
+        gslope = None
+        if has_slope:   # the gradient arriving at pout goes back through the PReLU and joins the gradient of out
+            gslope = _pgrad(slope_p) if need[4] else None
+            g = _prelu_backward(gpout.contiguous(), out, None, slope, gres=g, gslope=gslope)
+        gs = gw = gb = None
+        if need[0]:
+            gs, _ = _tconv3_run(g, weight, transposed=True)
+        if need[1] or (has_bias and need[2]):
+            gw = _pgrad(weight_p)
+            gb = _pgrad(bias_p) if has_bias else None
+            _tconv3_wgrad(s, g, gw, gb)
+        return gs, gw, gb, (g if has_res and need[3] else None), gslope
+
+
+def tconv3(s, conv3d, residual=None, prelu_mod=None):
+    """A (3,1,1) ``nn.Conv3d`` (padding (1,0,0)) on frame-major s [T, B, C, H, W] [+ residual]; with ``prelu_mod`` (an ``nn.PReLU()``)
+    returns (out, prelu(out)), the activation in the same kernel."""
+    return _TConv3.apply(s, conv3d.weight, conv3d.bias, residual, None if prelu_mod is None else prelu_mod.weight)
+
+
+class _FRBFused(Function):
+    """x + conv3d_2(conv3d_1(prelu(x))) as ONE autograd node (FRB, FSTRN_arch.py:11-22) on frame-major x: the PReLU (unless `px`, its
+    output, arrives from the previous block's kernel), the (1,3,3) convolution as a 3x3 convolution over T * B images, and the temporal
+    convolution with x as its fused residual and -- given the NEXT block's slope -- that block's PReLU as a second output.  Backward: the
+    gradient arriving at pout goes through the PReLU with gout as the fused skip gradient; the block's own PReLU backward adds the skip
+    gradient the same way, so no identity gradient costs a pass of its own."""
+
+    @staticmethod
+    def forward(ctx, x, px, slope, w1, b1, w2, b2, next_slope):
+        _need_cuda(x, px, slope, w1, b1, w2, b2, next_slope)
+        x, px, slope, w1, b1, w2, b2, next_slope = _c(x), _c(px), _c(_slope(slope)), _c(w1), _c(b1), _c(w2), _c(b2), _c(_slope(next_slope))
+        T, B, C, H, W = x.shape
+        if tuple(w1.shape) != (C, C, 1, 3, 3) or tuple(w2.shape) != (C, C, 3, 1, 1):
+            raise RuntimeError('frb: expected a %dx%dx(1,3,3) and a %dx%dx(3,1,1) conv, got %s and %s' % (C, C, C, C, tuple(w1.shape), tuple(w2.shape)))
+        own = px is None
+        if own:
+            px = _prelu_forward(x, None, slope)
+        w1s = w1[:, :, 0]   # (a view with the 2-D layout: the middle dimension has one element)
+        h = torch.empty_like(x)
+        _conv(px, w1s, h, bias=b1, what='frb conv3d_1')
+        out, pout = _tconv3_run(h, w2, b2, x, next_slope)
+        ctx.own, ctx.has_next = own, next_slope is not None
+        ctx.params = (slope, w1, b1, w2, b2, next_slope)   # only to find their gradient buffers (_pgrad)
+        ctx.save_for_backward(x if own else None, px, h, out if next_slope is not None else None, slope, w1, w2, next_slope)
+        if next_slope is None:
+            return out
+        return out, pout
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, gpout=None):
+        x, px, h, out, slope, w1, w2, next_slope = ctx.saved_tensors
+        slope_p, w1_p, b1_p, w2_p, b2_p, next_p = ctx.params
+        need = ctx.needs_input_grad
+        g = gout.contiguous()
+        gnext = None
+        if ctx.has_next:
+            gnext = _pgrad(next_p) if need[7] else None
+            g = _prelu_backward(gpout.contiguous(), out, None, next_slope, gres=g, gslope=gnext)
+        gw1 = gb1 = gw2 = gb2 = gslope = gx = gpx = None
+        if need[5] or need[6]:   # (the weight-gradient kernels produce weight and bias gradient in one call, as in the conv nodes above)
+            gw2 = _pgrad(w2_p)
+            gb2 = _pgrad(b2_p) if b2_p is not None else None
+            _tconv3_wgrad(h, g, gw2, gb2)
+        # what lies below conv3d_2: the gradient of px, wanted by this block's own PReLU (for x or the slope) or by the previous block's node
+        need_gpx = (need[0] or need[2]) if ctx.own else need[1]
+        if need[3] or need[4] or need_gpx:
+            gh, _ = _tconv3_run(g, w2, transposed=True)
+            if need[3] or need[4]:
+                gw1 = _pgrad(w1_p)
+                gb1 = _pgrad(b1_p) if b1_p is not None else None
+                _conv_wgrad(px, gh, gw1[:, :, 0], gb1, what='frb wgrad1')
+            if need_gpx:
+                gpx = torch.empty_like(px)
+                _conv(gh, w1[:, :, 0], gpx, transposed=True, what='frb dgrad1')
+        if ctx.own:   # through this block's own PReLU, the skip gradient added in the same pass
+            if need_gpx:
+                gslope = _pgrad(slope_p) if need[2] else None
+                gx = _prelu_backward(gpx, x, None, slope, gres=g, gslope=gslope, need_gx=need[0])
+            gpx = None
+        elif need[0]:   # x and px are the two outputs of the previous block's node: the skip gradient and the PReLU's, separately
+            gx = g
+        gw1, gb1 = (gw1 if need[3] else None), (gb1 if need[4] else None)
+        gw2, gb2 = (gw2 if need[5] else None), (gb2 if need[6] else None)
+        return gx, gpx, gslope, gw1, gb1, gw2, gb2, gnext
+
+
+def frb(x, prelu_mod, conv1, conv2, px=None, next_prelu=None):
+    """One FRB on frame-major x [T, B, C, H, W]: x + conv2(conv1(prelu(x))).  px: prelu(x) when the previous block's kernel has already
+    produced it; next_prelu: the next block's ``nn.PReLU()`` -- the call then returns (out, next_prelu(out))."""
+    return _FRBFused.apply(x, px, None if px is not None else prelu_mod.weight, conv1.weight, conv1.bias, conv2.weight, conv2.bias,
+                           None if next_prelu is None else next_prelu.weight)
+
+
+class _ConvT1x1(Function):
+    """``nn.ConvTranspose3d(Ci, Co, (1,1,1))`` on [..., Ci, H, W]: a 1x1 convolution with the transposed weight (Ci, Co, 1, 1, 1)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _need_cuda(x, weight, bias)
+        x, weight, bias = _c(x), _c(weight), _c(bias)
+        Ci, Co = weight.shape[:2]
+        if x.shape[-3] != Ci or weight.numel() != Ci * Co:
+            raise RuntimeError('conv_transpose1x1: x %s and weight %s do not fit' % (tuple(x.shape), tuple(weight.shape)))
+        out = x.new_empty(*x.shape[:-3], Co, *x.shape[-2:])
+        _conv(x, weight.view(Ci, Co, 1, 1), out, bias=bias, transposed=True, what='conv_transpose1x1')
+        ctx.params = (weight, bias)   # only to find their gradient buffers (_pgrad)
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, weight = ctx.saved_tensors
+        weight_p, bias_p = ctx.params
+        Ci, Co = weight.shape[:2]
+        gout = gout.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _conv(gout, weight.view(Ci, Co, 1, 1), gx, what='conv_transpose1x1 dgrad')
+        if ctx.needs_input_grad[1] or (bias_p is not None and ctx.needs_input_grad[2]):
+            # the 1x1 weight-gradient kernel gives (Co, Ci) and the bias gradient of gout; the parameter is stored (Ci, Co)
+            gwt = x.new_empty(Co, Ci, 1, 1)
+            gb = _pgrad(bias_p) if bias_p is not None else None
+            _conv_wgrad(x, gout, gwt, gb, what='conv_transpose1x1 wgrad')
+            gw = _pgrad(weight_p)
+            gw.view(Ci, Co).copy_(gwt.view(Co, Ci).t())
+        return gx, gw, gb
+
+
+def conv_transpose1x1(x, convt):
+    """A kernel-1 / stride-1 ``nn.ConvTranspose3d`` (or 2d) on [..., C, H, W]."""
+    if any(k != 1 for k in convt.kernel_size) or any(st != 1 for st in convt.stride):
+        raise NotImplementedError('conv_transpose1x1: kernel %s / stride %s; only kernel 1, stride 1 is on the MI355X path'
+                                  % (tuple(convt.kernel_size), tuple(convt.stride)))
+    return _ConvT1x1.apply(x, convt.weight, convt.bias)
+
+
 # ------------------------------------------------------------------------------------------ device guard
 def _guarded(fn):
     """Run an operator on the device of its tensors: HIP launches go to the CURRENT device, and `_stream()` /
