@@ -27,7 +27,11 @@ CASES = [
     (3, 1, 64, 64, 13, 22, False, 0.25),    # 64 x 64 on the scalar path
     (2, 2, 64, 64, 9, 70, True, None),
     (5, 2, 64, 64, 20, 36, False, None),
+    # 2 x 1030 = 2060 work items on the 1024 workgroups the plan caps the grid at: every workgroup walks two or three items with one weight
+    # image; the last tile of a frame holds 56 pixels (two waves leave the walk's body at once, one is partly filled); the 16-byte path
+    (2, 2, 16, 16, 364, 362, True, 0.25),
 ]
+TC_SLOTS = 1024   # csrc/conv3d_plan.h
 
 
 def _ref_tconv(s, w, b, res):
@@ -119,9 +123,13 @@ def test_the_fused_kernel_takes_the_network_shapes():
     a = ctypes.c_void_p(t.data_ptr())
     for case in CASES:
         T, B, Ci, Co, H, W = case[:6]
-        vec = ctypes.c_int(-1)
-        assert L.rvsr_tconv3_plan(T, B, Ci, Co, H, W, a, a, a, a, ctypes.byref(vec), None) == 0, case
+        vec, grid = ctypes.c_int(-1), ctypes.c_int(-1)
+        assert L.rvsr_tconv3_plan(T, B, Ci, Co, H, W, a, a, a, a, ctypes.byref(vec), ctypes.byref(grid)) == 0, case
         assert vec.value == int(H * W % 4 == 0), case
+        # one workgroup per work item (128 pixels of one batch element) up to the cap; beyond it the workgroups walk
+        items = B * ((H * W + 127) // 128)
+        assert grid.value == (TC_SLOTS if case[:6] == (2, 2, 16, 16, 364, 362) else items), (case, grid.value, items)
+    assert sum(1 for c in CASES if c[1] * ((c[4] * c[5] + 127) // 128) > TC_SLOTS) == 1
 
 
 @pytest.mark.parametrize('case', [CASES[0], CASES[3], CASES[4], CASES[6]], ids=lambda c: '-'.join(str(v) for v in c))
