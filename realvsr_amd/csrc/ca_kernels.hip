@@ -14,17 +14,7 @@
 // from ca_plan.h.
 #include "ca_plan.h"
 
-#define CHECK_LAUNCH(name)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) FAIL(RVSR_ERR_LAUNCH, name " launch: %s", hipGetErrorString(e_));   \
-    } while (0)
-
-__device__ __forceinline__ float ca_wave_sum(float v) {   // butterfly: every lane ends with the same sum, in one fixed order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+#include "glue_common.h"
 
 // ---------------------------------------------------------------------------------------------
 // Plane sums: workgroup (plane, q) sums slice q of plane `plane` of u (DOT: of g * u) into part[plane * S + q].
@@ -32,7 +22,6 @@ __device__ __forceinline__ float ca_wave_sum(float v) {   // butterfly: every la
 template <int DOT>
 __global__ __launch_bounds__(CA_WG) void ca_pool_kernel(const float* __restrict__ u, const float* __restrict__ g, float* __restrict__ part,
                                                         int HW, int S, int chunk, int vec) {
-    __shared__ float red[CA_WG / 64];
     const unsigned plane = blockIdx.x / (unsigned)S, q = blockIdx.x - plane * (unsigned)S;
     const int lo = (int)q * chunk, hi = lo + chunk < HW ? lo + chunk : HW, tid = threadIdx.x;
     const float* pu = u + (size_t)plane * HW + lo;
@@ -83,10 +72,7 @@ __global__ __launch_bounds__(CA_WG) void ca_pool_kernel(const float* __restrict_
         }
         for (; i < n; i += CA_WG) s0 += DOT ? pu[i] * pg[i] : pu[i];
     }
-    const float w = ca_wave_sum((s0 + s1) + (s2 + s3));
-    if ((tid & 63) == 0) red[tid >> 6] = w;
-    __syncthreads();
-    if (tid == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum4_to((s0 + s1) + (s2 + s3), part + blockIdx.x);
 }
 
 // dst = (X ? x : 0) + k * src + add over one slice of one plane
@@ -171,14 +157,14 @@ __global__ __launch_bounds__(CA_WG) void ca_scale_kernel(const float* __restrict
     for (int j = wave; j < Cr; j += CA_WG / 64) {
         float acc = 0.f;
         for (int cc = lane; cc < C; cc += 64) acc = fmaf(w1[(size_t)j * C + cc], sS[cc], acc);
-        acc = ca_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) sZ[j] = fmaxf(acc + b1[j], 0.f);
     }
     __syncthreads();
     if (wave == 0) {
         float acc = 0.f;
         for (int j = lane; j < Cr; j += 64) acc = fmaf(w2[(size_t)c * Cr + j], sZ[j], acc);
-        acc = ca_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) sA[0] = 1.f / (1.f + expf(-(acc + b2[c])));
     }
     __syncthreads();
@@ -318,8 +304,7 @@ extern "C" int rvsr_channel_attention_forward(const float* u, const float* x, co
     else
         hipLaunchKernelGGL(ca_scale_kernel<0>, grid, dim3(CA_WG), lds, st, u, x, part, w1, b1, w2, b2, out, pooled, hidden, gate, C, Cr, HW,
                            p.slices, p.chunk, p.vec, res_scale, 1.f / (float)HW);
-    CHECK_LAUNCH("ca_scale");
-    return RVSR_OK;
+    RETURN_LAUNCH("ca_scale");
 }
 
 extern "C" int rvsr_channel_attention_backward(const float* gout, const float* u, const float* w1, const float* w2, const float* pooled,
@@ -344,6 +329,5 @@ extern "C" int rvsr_channel_attention_backward(const float* gout, const float* u
                        gb2, B, C, Cr, p.slices, res_scale, 1.f / (float)HW);
     CHECK_LAUNCH("ca_bwd_gate");
     hipLaunchKernelGGL(ca_bwd_scale_kernel, grid, dim3(CA_WG), 0, st, gout, gate, gs, gu, HW, p.slices, p.chunk, p.vec, res_scale);
-    CHECK_LAUNCH("ca_bwd_scale");
-    return RVSR_OK;
+    RETURN_LAUNCH("ca_bwd_scale");
 }

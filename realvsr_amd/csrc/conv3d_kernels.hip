@@ -19,12 +19,7 @@
 #include "conv3d_plan.h"
 
 #include "bf16x3.h"
-
-#define CHECK_LAUNCH(name)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) FAIL(RVSR_ERR_LAUNCH, name " launch: %s", hipGetErrorString(e_));   \
-    } while (0)
+#include "glue_common.h"
 
 struct TcParams {
     const float* s;
@@ -282,8 +277,7 @@ static int tc_launch(const TcParams& p, int grid, int f32, hipStream_t st) {
     auto k = f32 ? (p.vec ? tconv3_kernel<KS, MT, true, true> : tconv3_kernel<KS, MT, true, false>)
                  : (p.vec ? tconv3_kernel<KS, MT, false, true> : tconv3_kernel<KS, MT, false, false>);
     hipLaunchKernelGGL(k, dim3(grid), dim3(TC_WG), 0, st, p);
-    CHECK_LAUNCH("tconv3");
-    return RVSR_OK;
+    RETURN_LAUNCH("tconv3");
 }
 
 extern "C" int rvsr_tconv3_plan(int T, int B, int Ci, int Co, int H, int W, const void* s, const void* residual, const void* out,
@@ -322,12 +316,6 @@ extern "C" int rvsr_tconv3_forward(const float* s, const float* w, const float* 
 
 // ---------------------------------------------------------------------------------------------
 // PReLU.  One slope for the whole tensor (nn.PReLU()), always read from device memory.
-__device__ __forceinline__ float pr_wave_sum(float v) {   // butterfly: every lane ends with the same sum, in one fixed order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // y = prelu(a [+ b]) [* keep * scale]
 template <int VEC>
 __global__ __launch_bounds__(PR_WG) void prelu_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ slope,
@@ -368,7 +356,6 @@ template <int VEC>
 __global__ __launch_bounds__(PR_WG) void prelu_bwd_kernel(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ b,
                                                           const float* __restrict__ slope, const unsigned char* __restrict__ keep, float scale,
                                                           const float* gres, float* gx, float* __restrict__ part, size_t n) {
-    __shared__ float red[PR_WG / 64];
     const float sl = slope[0];
     const size_t first = (size_t)blockIdx.x * PR_WG + threadIdx.x, step = (size_t)gridDim.x * PR_WG;
     float acc = 0.f;
@@ -406,21 +393,14 @@ __global__ __launch_bounds__(PR_WG) void prelu_bwd_kernel(const float* __restric
             acc += gg * (x > 0.f ? 0.f : x);
         }
     }
-    const float w = pr_wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum4_to(acc, part + blockIdx.x);
 }
 
 // gslope[0] = sum of the `blocks` partials: one workgroup, an order fixed by `blocks` alone
 __global__ __launch_bounds__(PR_WG) void prelu_slope_kernel(const float* __restrict__ part, int blocks, float* __restrict__ gslope) {
-    __shared__ float red[PR_WG / 64];
     float acc = 0.f;
     for (int i = threadIdx.x; i < blocks; i += PR_WG) acc += part[i];
-    const float w = pr_wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) gslope[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum4_to(acc, gslope);
 }
 
 extern "C" size_t rvsr_prelu_workspace_bytes(void) { return pr_workspace_bytes(); }
@@ -444,8 +424,7 @@ extern "C" int rvsr_prelu_forward(const float* a, const float* b, const float* s
         hipLaunchKernelGGL(prelu_fwd_kernel<1>, dim3(q.blocks), dim3(PR_WG), 0, st, a, b, slope, keep, scale, y, n);
     else
         hipLaunchKernelGGL(prelu_fwd_kernel<0>, dim3(q.blocks), dim3(PR_WG), 0, st, a, b, slope, keep, scale, y, n);
-    CHECK_LAUNCH("prelu_forward");
-    return RVSR_OK;
+    RETURN_LAUNCH("prelu_forward");
 }
 
 extern "C" int rvsr_prelu_backward(const float* g, const float* a, const float* b, const float* slope, const unsigned char* keep, float scale,

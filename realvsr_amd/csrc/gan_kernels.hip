@@ -5,16 +5,7 @@
 //
 // Reductions follow the project's convention: double accumulators, a fixed split of the work over workgroups, a fixed
 // LDS tree inside a workgroup and a fixed-order sum over the partials -> bit-identical results from run to run.
-#include "rvsr_common.h"
-
-#define LOOP(i, n) for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-#define GRID_FOR(n) dim3((unsigned)(((n) + 255) / 256 > 4096 ? 4096 : ((n) + 255) / 256))
-#define CHECK_LAUNCH(name)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) FAIL(RVSR_ERR_LAUNCH, name " launch: %s", hipGetErrorString(e_));   \
-        return RVSR_OK;                                                                           \
-    } while (0)
+#include "glue_common.h"
 
 // ---------------------------------------------------------------- BatchNorm2d + LeakyReLU
 // Per channel the B*HW elements are cut into NP equal slices (NP from the size alone); workgroup (q, c) reduces slice q of
@@ -182,7 +173,7 @@ extern "C" int rvsr_bn_lrelu_forward(const float* x, const float* gamma, const f
                        running_var, num_batches_tracked, momentum, eps, save_mean, save_invstd, coef);
     const size_t total = (size_t)n * C;
     hipLaunchKernelGGL(bn_apply_kernel, GRID_FOR(total), dim3(256), 0, st, x, coef, y, C, HW, total, slope);
-    CHECK_LAUNCH("bn_lrelu_forward");
+    RETURN_LAUNCH("bn_lrelu_forward");
 }
 
 extern "C" int rvsr_bn_lrelu_backward(const float* gy, const float* y, const float* x, const float* gamma, const float* save_mean,
@@ -205,7 +196,7 @@ extern "C" int rvsr_bn_lrelu_backward(const float* gy, const float* y, const flo
         hipLaunchKernelGGL(bn_bwd_apply_kernel, GRID_FOR(total), dim3(256), 0, st, gy, y, x, save_mean, save_invstd, coef, gx, C, HW,
                            total, slope);
     }
-    CHECK_LAUNCH("bn_lrelu_backward");
+    RETURN_LAUNCH("bn_lrelu_backward");
 }
 
 // ---------------------------------------------------------------- BCE-with-logits GAN criterion
@@ -273,7 +264,7 @@ extern "C" int rvsr_gan_loss_forward(const float* a, size_t na, const float* b, 
     if (!a || !out || !saved || na == 0) FAIL(RVSR_ERR_BAD_ARG, "gan_loss: null / empty argument");
     if (b != nullptr && nb == 0) FAIL(RVSR_ERR_BAD_ARG, "gan_loss: empty relativistic operand");
     hipLaunchKernelGGL(gan_loss_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, na, b, nb, target, scale, out, saved);
-    CHECK_LAUNCH("gan_loss_forward");
+    RETURN_LAUNCH("gan_loss_forward");
 }
 
 extern "C" int rvsr_gan_loss_backward(const float* a, size_t na, size_t nb, const float* saved, const float* gscalar, float target,
@@ -283,5 +274,5 @@ extern "C" int rvsr_gan_loss_backward(const float* a, size_t na, size_t nb, cons
     const size_t n = na > nb ? na : nb;
     hipLaunchKernelGGL(gan_loss_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, a, na, nb, saved, gscalar, target, scale, ga,
                        gb);
-    CHECK_LAUNCH("gan_loss_backward");
+    RETURN_LAUNCH("gan_loss_backward");
 }

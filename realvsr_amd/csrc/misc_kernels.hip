@@ -3,17 +3,15 @@
 //   * MaxPool2d(3,2,1) + AvgPool2d(3,2,1) written as one concatenated tensor   EDVR_arch.py:188-194
 //   * TSA temporal attention: correlation + sigmoid + modulation              EDVR_arch.py:171-181
 //   * TSA output: fea * sigmoid(att) * 2 + att_add                            EDVR_arch.py:204-207
-//   * Laplacian pyramid: reflect-pad 5x5 binomial + ::2 select, zero-insert upsample + diff
-//                                                                             utils/util.py:503-554
-//   * Charbonnier loss sum + gradient                                         loss.py:17-23
+//   * every reflect-padded 5x5 binomial stencil of the Laplacian pyramid: blur + ::2 select, zero-insert upsample + diff, and
+//     conv_gauss / upsample as stand-alone operators                          utils/util.py:503-554
+//   * YCbCr -> BGR uint8 for the inference path, the MFMA rate aid of bench.py, and the library's error string (rvsr_last_error)
+// The scalar losses live in train_kernels.hip.
 // All kernels: one thread per output element, lanes along W (coalesced), grid-stride loops.
 // Backward kernels are gathers that re-evaluate the forward index map over a conservative
 // candidate window (no atomics -> deterministic).
 #define RVSR_DEFINE_REDUCE
-#include "rvsr_common.h"
-
-#define GRID_FOR(n) dim3((unsigned)(((n) + 255) / 256 > 4096 ? 4096 : ((n) + 255) / 256))
-#define LOOP(i, n) for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
+#include "glue_common.h"
 
 // ---------------------------------------------------------------- bilinear upsample
 struct Lerp {
@@ -395,54 +393,73 @@ __global__ void lap_updiff_bwd_kernel(const float* __restrict__ gout, float* __r
     }
 }
 
-// ---------------------------------------------------------------- Charbonnier
-__global__ void charb_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float eps,
-                                 double* __restrict__ partial) {
-    __shared__ double red[256];
-    double acc = 0.0;
-    LOOP(i, n) {
-        const float d = x[i] - y[i];
-        acc += (double)sqrtf(d * d + eps);
+// conv_gauss / upsample of the pyramid helpers as stand-alone operators (utils/util.py:503-516)
+// out[y][x] = gain/256 * sum k[i]k[j] Z[reflect(y+i-2)][reflect(x+j-2)];  up == 0: Z = in (H x W);
+// up == 1: Z = zero-insert of in (H/2 x W/2) at the even positions of an H x W grid
+__global__ void gauss_full_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int H, int W,
+                                      int up, float gain) {
+    const int Hs = up ? H / 2 : H, Ws = up ? W / 2 : W;
+    const size_t n = planes * H * W;
+    LOOP(idx, n) {
+        const int x = (int)(idx % W);
+        const int y = (int)((idx / W) % H);
+        const float* p = in + (idx / ((size_t)W * H)) * Hs * Ws;
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int r = reflect(y + i - 2, H);
+            if (up && (r & 1)) continue;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                const int s = reflect(x + j - 2, W);
+                if (up && (s & 1)) continue;
+                acc += (binom(i) * binom(j)) * p[(size_t)(up ? r >> 1 : r) * Ws + (up ? s >> 1 : s)];
+            }
+        }
+        out[idx] = acc * (gain * (1.f / 256.f));
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
-__global__ void charb_finish_kernel(const double* __restrict__ partial, int nb, double scale, float* __restrict__ out) {
-    __shared__ double red[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
-}
-// gx = (gscalar * scale) * d / sqrt(d^2 + eps); gscalar read from device memory (no host sync)
-__global__ void charb_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gs,
-                                 float scale, float eps, float* __restrict__ gx, size_t n) {
-    const float k = gs[0] * scale;
-    LOOP(i, n) {
-        const float d = x[i] - y[i];
-        gx[i] = k * d / sqrtf(d * d + eps);
+// adjoint: gin[a][b] = gain/256 * sum over outputs (y, x) in a 5x5 neighbourhood of the taps that land on Z[r][s],
+// (r, s) = (a, b) (up == 0) or (2a, 2b) (up == 1).  Reflection keeps |y - r| <= 2.
+__global__ void gauss_full_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin, size_t planes, int H, int W,
+                                      int up, float gain) {
+    const int Hs = up ? H / 2 : H, Ws = up ? W / 2 : W;
+    const size_t n = planes * Hs * Ws;
+    LOOP(idx, n) {
+        const int b = (int)(idx % Ws);
+        const int a = (int)((idx / Ws) % Hs);
+        const float* g = gout + (idx / ((size_t)Ws * Hs)) * H * W;
+        const int r = up ? 2 * a : a, s = up ? 2 * b : b;
+        float wy[5], wx[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int y = r - 2 + t, x = s - 2 + t;
+            float u = 0.f, v = 0.f;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                if (y >= 0 && y < H && reflect(y + i - 2, H) == r) u += binom(i);
+                if (x >= 0 && x < W && reflect(x + i - 2, W) == s) v += binom(i);
+            }
+            wy[t] = u;
+            wx[t] = v;
+        }
+        float acc = 0.f;
+#pragma unroll
+        for (int ty = 0; ty < 5; ++ty) {
+            if (wy[ty] == 0.f) continue;
+            float rowacc = 0.f;
+#pragma unroll
+            for (int tx = 0; tx < 5; ++tx)
+                if (wx[tx] != 0.f) rowacc += wx[tx] * g[(size_t)(r - 2 + ty) * W + s - 2 + tx];
+            acc += wy[ty] * rowacc;
+        }
+        gin[idx] = acc * (gain * (1.f / 256.f));
     }
 }
 
 // ---------------------------------------------------------------- host side
 thread_local char rvsr_g_err[256] = "";
 extern "C" const char* rvsr_last_error() { return rvsr_g_err; }
-#define CHECK_LAUNCH(name)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) FAIL(RVSR_ERR_LAUNCH, name " launch: %s", hipGetErrorString(e_));   \
-        return RVSR_OK;                                                                           \
-    } while (0)
 
 extern "C" int rvsr_upsample_bilinear_forward(const float* in, float* out, size_t planes, int H, int W, int factor,
                                               float scale, void* stream) {
@@ -450,10 +467,10 @@ extern "C" int rvsr_upsample_bilinear_forward(const float* in, float* out, size_
     const size_t n = planes * H * factor * W * factor;
     if (factor == 2 && n < (1ull << 32) && (((uintptr_t)out) & 7) == 0) {
         hipLaunchKernelGGL(upsample2_fwd_kernel, GRID_FOR(n / 4), dim3(256), 0, (hipStream_t)stream, in, out, (unsigned)planes, H, W, scale);
-        CHECK_LAUNCH("upsample2_fwd");
+        RETURN_LAUNCH("upsample2_fwd");
     }
     hipLaunchKernelGGL(upsample_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, factor, scale);
-    CHECK_LAUNCH("upsample_fwd");
+    RETURN_LAUNCH("upsample_fwd");
 }
 extern "C" int rvsr_upsample_bilinear_backward(const float* gout, float* gin, size_t planes, int H, int W, int factor,
                                                float scale, void* stream) {
@@ -461,10 +478,10 @@ extern "C" int rvsr_upsample_bilinear_backward(const float* gout, float* gin, si
     const size_t n = planes * H * W;
     if (factor == 2 && n * 4 < (1ull << 32) && (((uintptr_t)gout) & 7) == 0) {
         hipLaunchKernelGGL(upsample2_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, (unsigned)planes, H, W, scale);
-        CHECK_LAUNCH("upsample2_bwd");
+        RETURN_LAUNCH("upsample2_bwd");
     }
     hipLaunchKernelGGL(upsample_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, H, W, factor, scale);
-    CHECK_LAUNCH("upsample_bwd");
+    RETURN_LAUNCH("upsample_bwd");
 }
 extern "C" int rvsr_maxavgpool_forward(const float* in, float* out, unsigned char* argmax, int B, int C, int H, int W,
                                        void* stream) {
@@ -472,7 +489,7 @@ extern "C" int rvsr_maxavgpool_forward(const float* in, float* out, unsigned cha
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t n = (size_t)B * C * Ho * Wo;
     hipLaunchKernelGGL(pool_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, argmax, B, C, H, W, Ho, Wo);
-    CHECK_LAUNCH("pool_fwd");
+    RETURN_LAUNCH("pool_fwd");
 }
 extern "C" int rvsr_maxavgpool_backward(const float* gout, const unsigned char* argmax, float* gin, int B, int C, int H,
                                         int W, void* stream) {
@@ -480,7 +497,7 @@ extern "C" int rvsr_maxavgpool_backward(const float* gout, const unsigned char* 
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t n = (size_t)B * C * H * W;
     hipLaunchKernelGGL(pool_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, argmax, gin, B, C, H, W, Ho, Wo);
-    CHECK_LAUNCH("pool_bwd");
+    RETURN_LAUNCH("pool_bwd");
 }
 extern "C" int rvsr_tsa_temporal_forward(const float* emb, const float* emb_ref, const float* aligned, float* mod,
                                          float* prob, int B, int N, int C, int H, int W, int frame_major, void* stream) {
@@ -488,7 +505,7 @@ extern "C" int rvsr_tsa_temporal_forward(const float* emb, const float* emb_ref,
     const size_t n = (size_t)B * N * H * W;
     hipLaunchKernelGGL(tsa_corr_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, emb, emb_ref, aligned, mod, prob, B, N,
                        C, (size_t)H * W, frame_major);
-    CHECK_LAUNCH("tsa_corr_fwd");
+    RETURN_LAUNCH("tsa_corr_fwd");
 }
 extern "C" int rvsr_tsa_temporal_backward(const float* gmod, const float* emb, const float* emb_ref, const float* aligned,
                                           const float* prob, float* galigned, float* gemb, float* gemb_ref, int B, int N,
@@ -499,33 +516,33 @@ extern "C" int rvsr_tsa_temporal_backward(const float* gmod, const float* emb, c
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(tsa_corr_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gmod, emb, emb_ref, aligned, prob,
                        galigned, gemb, gemb_ref, B, N, C, (size_t)H * W, frame_major);
-    CHECK_LAUNCH("tsa_corr_bwd");
+    RETURN_LAUNCH("tsa_corr_bwd");
 }
 extern "C" int rvsr_tsa_output_forward(const float* fea, const float* att, const float* att_add, float* out, size_t n,
                                        void* stream) {
     if (!fea || !att || !att_add || !out) FAIL(RVSR_ERR_BAD_ARG, "tsa_output: null argument");
     hipLaunchKernelGGL(tsa_final_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, fea, att, att_add, out, n);
-    CHECK_LAUNCH("tsa_final_fwd");
+    RETURN_LAUNCH("tsa_final_fwd");
 }
 extern "C" int rvsr_tsa_output_backward(const float* g, const float* fea, const float* att, float* gfea, float* gatt,
                                         size_t n, void* stream) {
     if (!g || !fea || !att || !gfea || !gatt) FAIL(RVSR_ERR_BAD_ARG, "tsa_output backward: null argument");
     hipLaunchKernelGGL(tsa_final_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, g, fea, att, gfea, gatt, n);
-    CHECK_LAUNCH("tsa_final_bwd");
+    RETURN_LAUNCH("tsa_final_bwd");
 }
 extern "C" int rvsr_pyr_down_forward(const float* in, float* out, size_t planes, int H, int W, void* stream) {
     if (!in || !out || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "pyr_down: bad argument (reflect pad 2 needs H,W >= 3)");
     const int Hd = (H + 1) / 2, Wd = (W + 1) / 2;
     const size_t n = planes * Hd * Wd;
     hipLaunchKernelGGL(gauss_down_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, Hd, Wd);
-    CHECK_LAUNCH("gauss_down_fwd");
+    RETURN_LAUNCH("gauss_down_fwd");
 }
 extern "C" int rvsr_pyr_down_backward(const float* gout, float* gin, size_t planes, int H, int W, void* stream) {
     if (!gout || !gin || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "pyr_down backward: bad argument");
     const int Hd = (H + 1) / 2, Wd = (W + 1) / 2;
     const size_t n = planes * H * W;
     hipLaunchKernelGGL(gauss_down_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, H, W, Hd, Wd);
-    CHECK_LAUNCH("gauss_down_bwd");
+    RETURN_LAUNCH("gauss_down_bwd");
 }
 extern "C" int rvsr_pyr_updiff_forward(const float* cur, const float* down, float* out, size_t planes, int H, int W,
                                        void* stream) {
@@ -533,122 +550,38 @@ extern "C" int rvsr_pyr_updiff_forward(const float* cur, const float* down, floa
         FAIL(RVSR_ERR_BAD_ARG, "pyr_updiff: H, W must be even and >= 4 (got %dx%d)", H, W);
     const size_t n = planes * H * W;
     hipLaunchKernelGGL(lap_updiff_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, cur, down, out, planes, H, W);
-    CHECK_LAUNCH("lap_updiff_fwd");
+    RETURN_LAUNCH("lap_updiff_fwd");
 }
 extern "C" int rvsr_pyr_updiff_backward(const float* gout, float* gdown, size_t planes, int H, int W, void* stream) {
     if (!gout || !gdown || (H & 1) || (W & 1) || H < 4 || W < 4) FAIL(RVSR_ERR_BAD_ARG, "pyr_updiff backward: bad argument");
     const size_t n = planes * (H / 2) * (W / 2);
     hipLaunchKernelGGL(lap_updiff_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gdown, planes, H, W);
-    CHECK_LAUNCH("lap_updiff_bwd");
+    RETURN_LAUNCH("lap_updiff_bwd");
 }
-#define CHARB_BLOCKS 1024
-extern "C" size_t rvsr_charbonnier_workspace_bytes() { return CHARB_BLOCKS * sizeof(double); }
-extern "C" int rvsr_charbonnier_forward(const float* x, const float* y, size_t n, float eps, double scale, float* out,
-                                        void* workspace, void* stream) {
-    if (!x || !y || !out || !workspace) FAIL(RVSR_ERR_BAD_ARG, "charbonnier: null argument");
-    unsigned nb = (unsigned)((n + 255) / 256);
-    if (nb > CHARB_BLOCKS) nb = CHARB_BLOCKS;
-    if (nb == 0) nb = 1;
-    hipLaunchKernelGGL(charb_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, n, eps, (double*)workspace);
-    hipLaunchKernelGGL(charb_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, scale, out);
-    CHECK_LAUNCH("charbonnier_fwd");
+extern "C" int rvsr_conv_gauss_forward(const float* in, float* out, size_t planes, int H, int W, float gain, void* stream) {
+    if (!in || !out || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "conv_gauss: bad argument (reflect padding 2 needs H, W >= 3)");
+    const size_t n = planes * (size_t)H * W;
+    hipLaunchKernelGGL(gauss_full_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, 0, gain);
+    RETURN_LAUNCH("conv_gauss_fwd");
 }
-extern "C" int rvsr_charbonnier_backward(const float* x, const float* y, const float* gscalar, float scale, float eps,
-                                         float* gx, size_t n, void* stream) {
-    if (!x || !y || !gscalar || !gx) FAIL(RVSR_ERR_BAD_ARG, "charbonnier backward: null argument");
-    hipLaunchKernelGGL(charb_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, x, y, gscalar, scale, eps, gx, n);
-    CHECK_LAUNCH("charbonnier_bwd");
+extern "C" int rvsr_conv_gauss_backward(const float* gout, float* gin, size_t planes, int H, int W, float gain, void* stream) {
+    if (!gout || !gin || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "conv_gauss backward: bad argument");
+    const size_t n = planes * (size_t)H * W;
+    hipLaunchKernelGGL(gauss_full_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, H, W, 0, gain);
+    RETURN_LAUNCH("conv_gauss_bwd");
 }
-
-// ---------------------------------------------------------------- Gradient-weighted loss (GWLoss)
-// codes/models/loss.py:54-80: L = (1 + w|Sx(x1) - Sx(x2)|) (1 + w|Sy(x1) - Sy(x2)|) |x1 - x2| with depthwise 3x3 Sobel
-// filters and zero padding.  Sobel is linear, so only d = x1 - x2 is filtered.  One fused pass: 3x3 window of d,
-// loss term, block-reduced sum; when a gradient is wanted it also stores the three per-pixel factors the backward
-// gather needs (A = dL/dd through |d|, Bx / By = dL/dSx, dL/dSy).
-__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
-__global__ void gw_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2, size_t planes, int H, int W, float w,
-                              double* __restrict__ partial, float* __restrict__ fa, float* __restrict__ fbx,
-                              float* __restrict__ fby) {
-    __shared__ double red[256];
-    const size_t n = planes * H * W;
-    double acc = 0.0;
-    LOOP(i, n) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const size_t base = i - (size_t)y * W - x;
-        float d[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const int yy = y + a - 1, xx = x + b - 1;
-                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                const size_t j = in ? base + (size_t)yy * W + xx : i;
-                const float v = x1[j] - x2[j];
-                d[a][b] = in ? v : 0.f;
-            }
-        const float sx = (d[0][2] - d[0][0]) + 2.f * (d[1][2] - d[1][0]) + (d[2][2] - d[2][0]);
-        const float sy = (d[2][0] - d[0][0]) + 2.f * (d[2][1] - d[0][1]) + (d[2][2] - d[0][2]);
-        const float ax = 1.f + w * fabsf(sx), ay = 1.f + w * fabsf(sy), ad = fabsf(d[1][1]);
-        acc += (double)(ax * ay * ad);
-        if (fa != nullptr) {
-            fa[i] = ax * ay * sgnf(d[1][1]);
-            fbx[i] = w * sgnf(sx) * ay * ad;
-            fby[i] = ax * w * sgnf(sy) * ad;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+// in: planes x H x W  ->  out: planes x 2H x 2W
+extern "C" int rvsr_pyr_upsample_forward(const float* in, float* out, size_t planes, int H, int W, void* stream) {
+    if (!in || !out || H < 2 || W < 2) FAIL(RVSR_ERR_BAD_ARG, "pyr_upsample: bad argument");
+    const size_t n = planes * (size_t)H * W * 4;
+    hipLaunchKernelGGL(gauss_full_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, 2 * H, 2 * W, 1, 4.f);
+    RETURN_LAUNCH("pyr_upsample_fwd");
 }
-
-// g_d[q] = k * (A[q] + sum_p Bx[p] * kx[q - p] + By[p] * ky[q - p]),  Sx(d)_p = sum_{a,b} kx[a][b] d[p + (a-1, b-1)]
-__global__ void gw_bwd_kernel(const float* __restrict__ fa, const float* __restrict__ fbx, const float* __restrict__ fby,
-                              const float* __restrict__ gs, float scale, float* __restrict__ gx, size_t planes, int H, int W) {
-    const float k = gs[0] * scale;
-    const size_t n = planes * H * W;
-    LOOP(i, n) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const size_t base = i - (size_t)y * W - x;
-        float acc = fa[i];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                // p = q - (a-1, b-1) is the pixel whose filter tap (a, b) lands on q
-                const int yy = y - (a - 1), xx = x - (b - 1);
-                if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-                const size_t j = base + (size_t)yy * W + xx;
-                const float kx = (b == 0 ? -1.f : (b == 2 ? 1.f : 0.f)) * (a == 1 ? 2.f : 1.f);
-                const float ky = (a == 0 ? -1.f : (a == 2 ? 1.f : 0.f)) * (b == 1 ? 2.f : 1.f);
-                acc += fbx[j] * kx + fby[j] * ky;
-            }
-        gx[i] = k * acc;
-    }
-}
-
-extern "C" int rvsr_gwloss_forward(const float* x1, const float* x2, size_t planes, int H, int W, float w, double scale,
-                                   float* out, float* fa, float* fbx, float* fby, void* workspace, void* stream) {
-    if (!x1 || !x2 || !out || !workspace) FAIL(RVSR_ERR_BAD_ARG, "gwloss: null argument");
-    if ((fa == nullptr) != (fbx == nullptr) || (fa == nullptr) != (fby == nullptr)) FAIL(RVSR_ERR_BAD_ARG, "gwloss: factor buffers must be given together");
-    const size_t n = planes * H * W;
-    unsigned nb = (unsigned)((n + 255) / 256);
-    if (nb > CHARB_BLOCKS) nb = CHARB_BLOCKS;
-    if (nb == 0) nb = 1;
-    hipLaunchKernelGGL(gw_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x1, x2, planes, H, W, w, (double*)workspace, fa, fbx, fby);
-    hipLaunchKernelGGL(charb_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, scale, out);
-    CHECK_LAUNCH("gwloss_fwd");
-}
-extern "C" int rvsr_gwloss_backward(const float* fa, const float* fbx, const float* fby, const float* gscalar, float scale,
-                                    float* gx, size_t planes, int H, int W, void* stream) {
-    if (!fa || !fbx || !fby || !gscalar || !gx) FAIL(RVSR_ERR_BAD_ARG, "gwloss backward: null argument");
-    const size_t n = planes * H * W;
-    hipLaunchKernelGGL(gw_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, fa, fbx, fby, gscalar, scale, gx, planes, H, W);
-    CHECK_LAUNCH("gwloss_bwd");
+extern "C" int rvsr_pyr_upsample_backward(const float* gout, float* gin, size_t planes, int H, int W, void* stream) {
+    if (!gout || !gin || H < 2 || W < 2) FAIL(RVSR_ERR_BAD_ARG, "pyr_upsample backward: bad argument");
+    const size_t n = planes * (size_t)H * W;
+    hipLaunchKernelGGL(gauss_full_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, 2 * H, 2 * W, 1, 4.f);
+    RETURN_LAUNCH("pyr_upsample_bwd");
 }
 
 // ---------------------------------------------------------------- YCbCr (planar f32) -> BGR uint8 (HWC)
@@ -684,7 +617,7 @@ extern "C" int rvsr_ycbcr_to_bgr_u8(const float* ycc, unsigned char* bgr, int H,
     if (!ycc || !bgr || H <= 0 || W <= 0) FAIL(RVSR_ERR_BAD_ARG, "ycbcr_to_bgr_u8: null/empty argument");
     const size_t hw = (size_t)H * W;
     hipLaunchKernelGGL(ycbcr2bgr_u8_kernel, GRID_FOR(hw), dim3(256), 0, (hipStream_t)stream, ycc, bgr, hw);
-    CHECK_LAUNCH("ycbcr_to_bgr_u8");
+    RETURN_LAUNCH("ycbcr_to_bgr_u8");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -714,5 +647,5 @@ __global__ __launch_bounds__(512) void mfma_rate_kernel(const dbg_bf16x8* __rest
 extern "C" int rvsr_debug_mfma_rate(const void* ops, float* out, int workgroups, int iters, void* stream) {
     if (!ops || !out || workgroups <= 0 || iters <= 0) FAIL(RVSR_ERR_BAD_ARG, "debug_mfma_rate: null/empty argument");
     hipLaunchKernelGGL(mfma_rate_kernel, dim3((unsigned)workgroups), dim3(512), 0, (hipStream_t)stream, (const dbg_bf16x8*)ops, out, iters);
-    CHECK_LAUNCH("debug_mfma_rate");
+    RETURN_LAUNCH("debug_mfma_rate");
 }

@@ -1,25 +1,28 @@
 // train_kernels.hip -- the HBM-bound operators either side of netG in one training step (gfx950):
-//   * SSIM low-frequency term of LapPyrLoss (loss.py:203,209 -> IQA_pytorch.SSIM, restated in oracle/ssim_oracle.py)
-//   * L1 / MSE / Huber / Charbonnier reductions (loss.py:10-40, PyramidLoss loss_mode :167-175)
-//   * conv_gauss(img, kernel) and upsample(x) of the pyramid helpers as stand-alone operators (utils/util.py:503-516)
+//   * every scalar loss: Charbonnier (loss.py:17-23), the gradient-weighted GWLoss (loss.py:54-80), the L1 / MSE / Huber /
+//     Charbonnier reductions (loss.py:10-40, PyramidLoss loss_mode :167-175) and the SSIM low-frequency term of LapPyrLoss
+//     (loss.py:203,209 -> IQA_pytorch.SSIM, restated in oracle/ssim_oracle.py)
 //   * Adam update on a flat parameter buffer (VideoSR_AllPair_model_YCbCr_Split.py:122-124,187: torch.optim.Adam)
 //   * CutBlur / channel-permute / blend augmentation of an LQ/GT clip pair in one pass
 //     (data/augments_video_allpair.py:6-88, called at VideoSR_AllPair_model_YCbCr_Split.py:169-173)
+//   * the broadcast add + activation of conv_cat_bcast and its adjoint
+// The pyramid stencils live in misc_kernels.hip.
 // One thread per output element, lanes along W (coalesced); reductions accumulate in double and finish in a second
 // one-block kernel (deterministic); backward kernels are gathers (no atomics).
-#include "rvsr_common.h"
+#include "glue_common.h"
 
-#define GRID_FOR(n) dim3((unsigned)(((n) + 255) / 256 > 4096 ? 4096 : ((n) + 255) / 256))
-#define LOOP(i, n) for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
+// ---------------------------------------------------------------- the reduction of every scalar loss
+// A forward kernel runs on red_blocks(n) workgroups of 256 threads; each leaves one double in the workspace (block_sum_to) and
+// affine_finish_kernel sums those in one workgroup.  Every order is fixed by n alone.
 #define RED_BLOCKS 1024
-#define CHECK_LAUNCH(name)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) FAIL(RVSR_ERR_LAUNCH, name " launch: %s", hipGetErrorString(e_));   \
-        return RVSR_OK;                                                                           \
-    } while (0)
-
-__device__ __forceinline__ void block_sum_to(double acc, double* __restrict__ partial) {
+static unsigned red_blocks(size_t n) {
+    unsigned nb = (unsigned)((n + 255) / 256);
+    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
+    if (nb == 0) nb = 1;
+    return nb;
+}
+// the sum of acc over the 256 threads of a workgroup, in every thread
+__device__ __forceinline__ double block_sum(double acc) {
     __shared__ double red[256];
     red[threadIdx.x] = acc;
     __syncthreads();
@@ -27,21 +30,22 @@ __device__ __forceinline__ void block_sum_to(double acc, double* __restrict__ pa
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    return red[0];
+}
+__device__ __forceinline__ void block_sum_to(double acc, double* __restrict__ partial) {
+    const double s = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 // out[0] = bias + scale * sum(partial)
 __global__ void affine_finish_kernel(const double* __restrict__ partial, int nb, double bias, double scale,
                                      float* __restrict__ out) {
-    __shared__ double red[256];
     double acc = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(bias + red[0] * scale);
+    const double s = block_sum(acc);
+    if (threadIdx.x == 0) out[0] = (float)(bias + s * scale);
+}
+static void launch_finish(const void* workspace, unsigned nb, double bias, double scale, float* out, void* stream) {
+    hipLaunchKernelGGL(affine_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, bias, scale, out);
 }
 
 // ---------------------------------------------------------------- element-wise losses
@@ -73,6 +77,90 @@ __global__ void pix_loss_bwd_kernel(const float* __restrict__ x, const float* __
                                     int mode, float param, float scale, float* __restrict__ gx, size_t n) {
     const float k = gs[0] * scale;
     LOOP(i, n) gx[i] = k * pix_loss_grad(x[i] - y[i], mode, param);
+}
+
+// ---------------------------------------------------------------- Charbonnier
+__global__ void charb_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float eps,
+                                 double* __restrict__ partial) {
+    double acc = 0.0;
+    LOOP(i, n) {
+        const float d = x[i] - y[i];
+        acc += (double)sqrtf(d * d + eps);
+    }
+    block_sum_to(acc, partial);
+}
+// gx = (gscalar * scale) * d / sqrt(d^2 + eps); gscalar read from device memory (no host sync)
+__global__ void charb_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gs,
+                                 float scale, float eps, float* __restrict__ gx, size_t n) {
+    const float k = gs[0] * scale;
+    LOOP(i, n) {
+        const float d = x[i] - y[i];
+        gx[i] = k * d / sqrtf(d * d + eps);
+    }
+}
+
+// ---------------------------------------------------------------- Gradient-weighted loss (GWLoss)
+// codes/models/loss.py:54-80: L = (1 + w|Sx(x1) - Sx(x2)|) (1 + w|Sy(x1) - Sy(x2)|) |x1 - x2| with depthwise 3x3 Sobel
+// filters and zero padding.  Sobel is linear, so only d = x1 - x2 is filtered.  One fused pass: 3x3 window of d,
+// loss term, block-reduced sum; when a gradient is wanted it also stores the three per-pixel factors the backward
+// gather needs (A = dL/dd through |d|, Bx / By = dL/dSx, dL/dSy).
+__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+__global__ void gw_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2, size_t planes, int H, int W, float w,
+                              double* __restrict__ partial, float* __restrict__ fa, float* __restrict__ fbx,
+                              float* __restrict__ fby) {
+    const size_t n = planes * H * W;
+    double acc = 0.0;
+    LOOP(i, n) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const size_t base = i - (size_t)y * W - x;
+        float d[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const int yy = y + a - 1, xx = x + b - 1;
+                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+                const size_t j = in ? base + (size_t)yy * W + xx : i;
+                const float v = x1[j] - x2[j];
+                d[a][b] = in ? v : 0.f;
+            }
+        const float sx = (d[0][2] - d[0][0]) + 2.f * (d[1][2] - d[1][0]) + (d[2][2] - d[2][0]);
+        const float sy = (d[2][0] - d[0][0]) + 2.f * (d[2][1] - d[0][1]) + (d[2][2] - d[0][2]);
+        const float ax = 1.f + w * fabsf(sx), ay = 1.f + w * fabsf(sy), ad = fabsf(d[1][1]);
+        acc += (double)(ax * ay * ad);
+        if (fa != nullptr) {
+            fa[i] = ax * ay * sgnf(d[1][1]);
+            fbx[i] = w * sgnf(sx) * ay * ad;
+            fby[i] = ax * w * sgnf(sy) * ad;
+        }
+    }
+    block_sum_to(acc, partial);
+}
+
+// g_d[q] = k * (A[q] + sum_p Bx[p] * kx[q - p] + By[p] * ky[q - p]),  Sx(d)_p = sum_{a,b} kx[a][b] d[p + (a-1, b-1)]
+__global__ void gw_bwd_kernel(const float* __restrict__ fa, const float* __restrict__ fbx, const float* __restrict__ fby,
+                              const float* __restrict__ gs, float scale, float* __restrict__ gx, size_t planes, int H, int W) {
+    const float k = gs[0] * scale;
+    const size_t n = planes * H * W;
+    LOOP(i, n) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const size_t base = i - (size_t)y * W - x;
+        float acc = fa[i];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                // p = q - (a-1, b-1) is the pixel whose filter tap (a, b) lands on q
+                const int yy = y - (a - 1), xx = x - (b - 1);
+                if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+                const size_t j = base + (size_t)yy * W + xx;
+                const float kx = (b == 0 ? -1.f : (b == 2 ? 1.f : 0.f)) * (a == 1 ? 2.f : 1.f);
+                const float ky = (a == 0 ? -1.f : (a == 2 ? 1.f : 0.f)) * (b == 1 ? 2.f : 1.f);
+                acc += fbx[j] * kx + fby[j] * ky;
+            }
+        gx[i] = k * acc;
+    }
 }
 
 // ---------------------------------------------------------------- SSIM
@@ -151,73 +239,6 @@ __global__ void ssim_bwd_kernel(const float* __restrict__ x, const float* __rest
             }
         }
         gx[idx] = k * (sa + 2.f * x[idx] * sb + y[idx] * sc);
-    }
-}
-
-// ---------------------------------------------------------------- conv_gauss / upsample as stand-alone operators
-__device__ __forceinline__ int reflect_idx(int q, int n) { return q < 0 ? -q : (q >= n ? 2 * (n - 1) - q : q); }
-__device__ __forceinline__ float binom5(int i) { return i == 0 || i == 4 ? 1.f : (i == 2 ? 6.f : 4.f); }
-
-// out[y][x] = gain/256 * sum k[i]k[j] Z[reflect(y+i-2)][reflect(x+j-2)];  up == 0: Z = in (H x W);
-// up == 1: Z = zero-insert of in (H/2 x W/2) at the even positions of an H x W grid
-__global__ void gauss_full_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int H, int W,
-                                      int up, float gain) {
-    const int Hs = up ? H / 2 : H, Ws = up ? W / 2 : W;
-    const size_t n = planes * H * W;
-    LOOP(idx, n) {
-        const int x = (int)(idx % W);
-        const int y = (int)((idx / W) % H);
-        const float* p = in + (idx / ((size_t)W * H)) * Hs * Ws;
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int r = reflect_idx(y + i - 2, H);
-            if (up && (r & 1)) continue;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const int s = reflect_idx(x + j - 2, W);
-                if (up && (s & 1)) continue;
-                acc += (binom5(i) * binom5(j)) * p[(size_t)(up ? r >> 1 : r) * Ws + (up ? s >> 1 : s)];
-            }
-        }
-        out[idx] = acc * (gain * (1.f / 256.f));
-    }
-}
-// adjoint: gin[a][b] = gain/256 * sum over outputs (y, x) in a 5x5 neighbourhood of the taps that land on Z[r][s],
-// (r, s) = (a, b) (up == 0) or (2a, 2b) (up == 1).  Reflection keeps |y - r| <= 2.
-__global__ void gauss_full_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin, size_t planes, int H, int W,
-                                      int up, float gain) {
-    const int Hs = up ? H / 2 : H, Ws = up ? W / 2 : W;
-    const size_t n = planes * Hs * Ws;
-    LOOP(idx, n) {
-        const int b = (int)(idx % Ws);
-        const int a = (int)((idx / Ws) % Hs);
-        const float* g = gout + (idx / ((size_t)Ws * Hs)) * H * W;
-        const int r = up ? 2 * a : a, s = up ? 2 * b : b;
-        float wy[5], wx[5];
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            const int y = r - 2 + t, x = s - 2 + t;
-            float u = 0.f, v = 0.f;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                if (y >= 0 && y < H && reflect_idx(y + i - 2, H) == r) u += binom5(i);
-                if (x >= 0 && x < W && reflect_idx(x + i - 2, W) == s) v += binom5(i);
-            }
-            wy[t] = u;
-            wx[t] = v;
-        }
-        float acc = 0.f;
-#pragma unroll
-        for (int ty = 0; ty < 5; ++ty) {
-            if (wy[ty] == 0.f) continue;
-            float rowacc = 0.f;
-#pragma unroll
-            for (int tx = 0; tx < 5; ++tx)
-                if (wx[tx] != 0.f) rowacc += wx[tx] * g[(size_t)(r - 2 + ty) * W + s - 2 + tx];
-            acc += wy[ty] * rowacc;
-        }
-        gin[idx] = acc * (gain * (1.f / 256.f));
     }
 }
 
@@ -332,26 +353,56 @@ __global__ void bcast_reduce_act_kernel(const float* __restrict__ gout, const fl
 }
 
 // ---------------------------------------------------------------- host side
+// (two names in the ABI for the one workspace every scalar loss takes)
 extern "C" size_t rvsr_reduce_workspace_bytes() { return RED_BLOCKS * sizeof(double); }
+extern "C" size_t rvsr_charbonnier_workspace_bytes() { return rvsr_reduce_workspace_bytes(); }
 
 extern "C" int rvsr_pixel_loss_forward(const float* x, const float* y, size_t n, int mode, float param, double scale, float* out,
                                        void* workspace, void* stream) {
     if (!x || !y || !out || !workspace) FAIL(RVSR_ERR_BAD_ARG, "pixel_loss: null argument");
     if (mode < 0 || mode > 3) FAIL(RVSR_ERR_BAD_ARG, "pixel_loss: mode %d (0 l1, 1 l2, 2 huber, 3 charbonnier)", mode);
-    unsigned nb = (unsigned)((n + 255) / 256);
-    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-    if (nb == 0) nb = 1;
+    const unsigned nb = red_blocks(n);
     hipLaunchKernelGGL(pix_loss_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, n, mode, param, (double*)workspace);
-    hipLaunchKernelGGL(affine_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, 0.0,
-                       scale, out);
-    CHECK_LAUNCH("pixel_loss_fwd");
+    launch_finish(workspace, nb, 0.0, scale, out, stream);
+    RETURN_LAUNCH("pixel_loss_fwd");
 }
 extern "C" int rvsr_pixel_loss_backward(const float* x, const float* y, const float* gscalar, int mode, float param, float scale,
                                         float* gx, size_t n, void* stream) {
     if (!x || !y || !gscalar || !gx) FAIL(RVSR_ERR_BAD_ARG, "pixel_loss backward: null argument");
     if (mode < 0 || mode > 3) FAIL(RVSR_ERR_BAD_ARG, "pixel_loss backward: mode %d", mode);
     hipLaunchKernelGGL(pix_loss_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, x, y, gscalar, mode, param, scale, gx, n);
-    CHECK_LAUNCH("pixel_loss_bwd");
+    RETURN_LAUNCH("pixel_loss_bwd");
+}
+extern "C" int rvsr_charbonnier_forward(const float* x, const float* y, size_t n, float eps, double scale, float* out,
+                                        void* workspace, void* stream) {
+    if (!x || !y || !out || !workspace) FAIL(RVSR_ERR_BAD_ARG, "charbonnier: null argument");
+    const unsigned nb = red_blocks(n);
+    hipLaunchKernelGGL(charb_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, n, eps, (double*)workspace);
+    launch_finish(workspace, nb, 0.0, scale, out, stream);
+    RETURN_LAUNCH("charbonnier_fwd");
+}
+extern "C" int rvsr_charbonnier_backward(const float* x, const float* y, const float* gscalar, float scale, float eps,
+                                         float* gx, size_t n, void* stream) {
+    if (!x || !y || !gscalar || !gx) FAIL(RVSR_ERR_BAD_ARG, "charbonnier backward: null argument");
+    hipLaunchKernelGGL(charb_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, x, y, gscalar, scale, eps, gx, n);
+    RETURN_LAUNCH("charbonnier_bwd");
+}
+extern "C" int rvsr_gwloss_forward(const float* x1, const float* x2, size_t planes, int H, int W, float w, double scale,
+                                   float* out, float* fa, float* fbx, float* fby, void* workspace, void* stream) {
+    if (!x1 || !x2 || !out || !workspace) FAIL(RVSR_ERR_BAD_ARG, "gwloss: null argument");
+    if ((fa == nullptr) != (fbx == nullptr) || (fa == nullptr) != (fby == nullptr)) FAIL(RVSR_ERR_BAD_ARG, "gwloss: factor buffers must be given together");
+    const size_t n = planes * H * W;
+    const unsigned nb = red_blocks(n);
+    hipLaunchKernelGGL(gw_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x1, x2, planes, H, W, w, (double*)workspace, fa, fbx, fby);
+    launch_finish(workspace, nb, 0.0, scale, out, stream);
+    RETURN_LAUNCH("gwloss_fwd");
+}
+extern "C" int rvsr_gwloss_backward(const float* fa, const float* fbx, const float* fby, const float* gscalar, float scale,
+                                    float* gx, size_t planes, int H, int W, void* stream) {
+    if (!fa || !fbx || !fby || !gscalar || !gx) FAIL(RVSR_ERR_BAD_ARG, "gwloss backward: null argument");
+    const size_t n = planes * H * W;
+    hipLaunchKernelGGL(gw_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, fa, fbx, fby, gscalar, scale, gx, planes, H, W);
+    RETURN_LAUNCH("gwloss_bwd");
 }
 
 static const SsimWin& ssim_window() {
@@ -377,13 +428,11 @@ extern "C" int rvsr_ssim_forward(const float* x, const float* y, size_t planes, 
     if ((ga == nullptr) != (gb == nullptr) || (ga == nullptr) != (gc == nullptr))
         FAIL(RVSR_ERR_BAD_ARG, "ssim: ga/gb/gc must be given together");
     const size_t n = planes * (size_t)(H - 10) * (W - 10);
-    unsigned nb = (unsigned)((n + 255) / 256);
-    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
+    const unsigned nb = red_blocks(n);
     hipLaunchKernelGGL(ssim_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, planes, H, W, ssim_window(),
                        (double*)workspace, ga, gb, gc);
-    hipLaunchKernelGGL(affine_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, 1.0,
-                       -scale, out);
-    CHECK_LAUNCH("ssim_fwd");
+    launch_finish(workspace, nb, 1.0, -scale, out, stream);
+    RETURN_LAUNCH("ssim_fwd");
 }
 extern "C" int rvsr_ssim_backward(const float* x, const float* y, const float* ga, const float* gb, const float* gc,
                                   const float* gscalar, float scale, float* gx, size_t planes, int H, int W, void* stream) {
@@ -392,33 +441,7 @@ extern "C" int rvsr_ssim_backward(const float* x, const float* y, const float* g
     const size_t n = planes * (size_t)H * W;
     hipLaunchKernelGGL(ssim_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, x, y, ga, gb, gc, gscalar, scale,
                        ssim_window(), gx, planes, H, W);
-    CHECK_LAUNCH("ssim_bwd");
-}
-
-extern "C" int rvsr_conv_gauss_forward(const float* in, float* out, size_t planes, int H, int W, float gain, void* stream) {
-    if (!in || !out || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "conv_gauss: bad argument (reflect padding 2 needs H, W >= 3)");
-    const size_t n = planes * (size_t)H * W;
-    hipLaunchKernelGGL(gauss_full_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, 0, gain);
-    CHECK_LAUNCH("conv_gauss_fwd");
-}
-extern "C" int rvsr_conv_gauss_backward(const float* gout, float* gin, size_t planes, int H, int W, float gain, void* stream) {
-    if (!gout || !gin || H < 3 || W < 3) FAIL(RVSR_ERR_BAD_ARG, "conv_gauss backward: bad argument");
-    const size_t n = planes * (size_t)H * W;
-    hipLaunchKernelGGL(gauss_full_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, H, W, 0, gain);
-    CHECK_LAUNCH("conv_gauss_bwd");
-}
-// in: planes x H x W  ->  out: planes x 2H x 2W
-extern "C" int rvsr_pyr_upsample_forward(const float* in, float* out, size_t planes, int H, int W, void* stream) {
-    if (!in || !out || H < 2 || W < 2) FAIL(RVSR_ERR_BAD_ARG, "pyr_upsample: bad argument");
-    const size_t n = planes * (size_t)H * W * 4;
-    hipLaunchKernelGGL(gauss_full_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, planes, 2 * H, 2 * W, 1, 4.f);
-    CHECK_LAUNCH("pyr_upsample_fwd");
-}
-extern "C" int rvsr_pyr_upsample_backward(const float* gout, float* gin, size_t planes, int H, int W, void* stream) {
-    if (!gout || !gin || H < 2 || W < 2) FAIL(RVSR_ERR_BAD_ARG, "pyr_upsample backward: bad argument");
-    const size_t n = planes * (size_t)H * W;
-    hipLaunchKernelGGL(gauss_full_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, planes, 2 * H, 2 * W, 1, 4.f);
-    CHECK_LAUNCH("pyr_upsample_bwd");
+    RETURN_LAUNCH("ssim_bwd");
 }
 
 extern "C" int rvsr_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float step_size,
@@ -429,7 +452,7 @@ extern "C" int rvsr_adam_step(float* param, const float* grad, float* exp_avg, f
     if (n == 0) return RVSR_OK;
     hipLaunchKernelGGL(adam_step_kernel, GRID_FOR((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
                        n, step_size, beta1, beta2, eps, weight_decay, bias_correction2_sqrt);
-    CHECK_LAUNCH("adam_step");
+    RETURN_LAUNCH("adam_step");
 }
 
 extern "C" int rvsr_augment_clips(const float* im1, const float* im2, float* out1, float* out2, const float* colour, size_t frames,
@@ -454,19 +477,19 @@ extern "C" int rvsr_augment_clips(const float* im1, const float* im2, float* out
     const size_t n = frames * 3 * (size_t)H * W;
     hipLaunchKernelGGL(augment_clips_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, im1, im2, out1, out2, colour, frames, H,
                        W, plan);
-    CHECK_LAUNCH("augment_clips");
+    RETURN_LAUNCH("augment_clips");
 }
 
 extern "C" int rvsr_bcast_add_act(float* a, const float* b, size_t per, int N, int act, float slope, void* stream) {
     if (!a || !b || N <= 0) FAIL(RVSR_ERR_BAD_ARG, "bcast_add_act: bad argument");
     if ((per & 3) != 0 || ((((uintptr_t)a) | ((uintptr_t)b)) & 15) != 0) FAIL(RVSR_ERR_BAD_ARG, "bcast_add_act: blocks must be 16-byte aligned multiples of 4 floats");
     hipLaunchKernelGGL(bcast_add_act_kernel, GRID_FOR(per / 4), dim3(256), 0, (hipStream_t)stream, a, b, per / 4, N, act, slope);
-    CHECK_LAUNCH("bcast_add_act");
+    RETURN_LAUNCH("bcast_add_act");
 }
 extern "C" int rvsr_bcast_reduce_act(const float* gout, const float* out, float* gb, size_t per, int N, float gslope, void* stream) {
     if (!gout || !gb || N <= 0) FAIL(RVSR_ERR_BAD_ARG, "bcast_reduce_act: bad argument");
     if ((per & 3) != 0 || ((((uintptr_t)gout) | ((uintptr_t)out) | ((uintptr_t)gb)) & 15) != 0)
         FAIL(RVSR_ERR_BAD_ARG, "bcast_reduce_act: blocks must be 16-byte aligned multiples of 4 floats");
     hipLaunchKernelGGL(bcast_reduce_act_kernel, GRID_FOR(per / 4), dim3(256), 0, (hipStream_t)stream, gout, out, gb, per / 4, N, gslope, out != nullptr);
-    CHECK_LAUNCH("bcast_reduce_act");
+    RETURN_LAUNCH("bcast_reduce_act");
 }

@@ -176,6 +176,40 @@ def _conv_wgrad(x1, gout, gw, gb, *, what, x2=None, gact=None, gact_slope=0.0, p
                                              Gh, Gw, _p(gw), _p(gb), Co, B, k, stride, Ho, Wo, 0, _p(ws), ws.numel(), _stream()), what)
 
 
+def _wgrad(x1, gout, weight, bias, *, what, **kw):
+    """The weight and bias gradient of a conv from its saved input `x1` and its output gradient, written where _pgrad puts the gradients
+    of the parameters `weight` and `bias` (None: the conv has no bias).  Returns (gw, gb); the keywords are _conv_wgrad's.  Only the first
+    and last dimension of gw are read, so a (Co, Ci, 1, k, k) Conv3d weight passes for its 2-D layout."""
+    gw = _pgrad(weight)
+    gb = _pgrad(bias) if bias is not None else None
+    _conv_wgrad(x1, gout, gw, gb, what=what, **kw)
+    return gw, gb
+
+
+def _res_chain_backward(node, g, skip, x, h, w1, b1, w2, b2, needs):
+    """Backward of h = relu(conv1(x)), u = conv2(h) given g = dL/du: (gx, gw1, gb1, gw2, gb2) for needs = (x, w1, b1, w2, b2).
+    gx = skip + dgrad1(...): conv1's data-gradient kernel adds `skip`, the gradient that reaches x past the two convs, as its fused
+    residual.  `node` prefixes the call names."""
+    need_x, need_w1, need_b1, need_w2, need_b2 = needs
+    gx = gw1 = gb1 = gw2 = gb2 = None
+    if need_w2 or need_b2:
+        gw2, gb2 = _wgrad(h, g, w2, b2, what=node + ' wgrad2')
+    if need_x or need_w1 or need_b1:
+        # gradient w.r.t. conv1's output: conv2's data gradient times relu'(h).  The mask is applied in that kernel's epilogue when it
+        # has one (8 x 64 tile; one extra read of h instead of a second read of h in BOTH consumers below), else by the consumers.
+        gh = torch.empty_like(x)
+        masked = _FUSE_GRAD_MASK and _conv(g, w2, gh, transposed=True, act=ACT_MASK, residual=h, what=node + ' dgrad2')
+        if not masked:
+            _conv(g, w2, gh, transposed=True, what=node + ' dgrad2')
+        hmask = None if masked else h
+        if need_w1 or need_b1:
+            gw1, gb1 = _wgrad(x, gh, w1, b1, gact=hmask, what=node + ' wgrad1')
+        if need_x:
+            gx = torch.empty_like(x)
+            _conv(gh, w1, gx, transposed=True, xact=hmask, residual=skip, what=node + ' dgrad1')
+    return gx, gw1, gb1, gw2, gb2
+
+
 # ------------------------------------------------------------------------------------------ conv
 class _Conv2dFused(Function):
     """act(conv2d(cat(x1, x2), w) + b) [+ residual] [-> PixelShuffle(2)]"""
@@ -257,10 +291,8 @@ class _Conv2dFused(Function):
                 ctx.dep_sink.buf = gx1
                 gx1 = None
         if need_w or (has_bias and ctx.needs_input_grad[3]):
-            gw = _pgrad(weight)
-            gb = _pgrad(ctx.bias_p) if has_bias else None
-            _conv_wgrad(x1, gout, gw, gb, x2=x2, gact=act_out, gact_slope=gslope, pixel_shuffled=ps, stride=stride,
-                        what='conv2d_backward_weight')
+            gw, gb = _wgrad(x1, gout, weight, ctx.bias_p, x2=x2, gact=act_out, gact_slope=gslope, pixel_shuffled=ps, stride=stride,
+                            what='conv2d_backward_weight')
         gres = gout if has_res else None
         return gx1, gx2, gw, gb, gres, None, None, None, None, None, None, None, None
 
@@ -283,7 +315,6 @@ class _ResBlockFused(Function):
         _conv(x, w1, h, bias=b1, act=ACT_RELU, what='res_block conv1')
         _conv(h, w2, out, bias=b2, residual=x, what='res_block conv2')
         ctx.save_for_backward(x, h, w1, w2)
-        ctx.has_bias = (b1 is not None, b2 is not None)
         ctx.bias_p = (b1, b2)   # only to find their gradient buffers (_pgrad)
         return out
 
@@ -292,28 +323,7 @@ class _ResBlockFused(Function):
     def backward(ctx, gout):
         x, h, w1, w2 = ctx.saved_tensors
         gout = gout.contiguous()
-        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad
-        gx = gw1 = gb1 = gw2 = gb2 = None
-        if need_w2 or need_b2:
-            gw2 = _pgrad(w2)
-            gb2 = _pgrad(ctx.bias_p[1]) if ctx.has_bias[1] else None
-            _conv_wgrad(h, gout, gw2, gb2, what='res_block wgrad2')
-        if need_x or need_w1 or need_b1:
-            # gradient w.r.t. conv1's output: conv2's data gradient times relu'(h).  The mask is applied in that kernel's epilogue when it
-            # has one (8 x 64 tile; one extra read of h instead of a second read of h in BOTH consumers below), else by the consumers.
-            gh = torch.empty_like(x)
-            masked = _FUSE_GRAD_MASK and _conv(gout, w2, gh, transposed=True, act=ACT_MASK, residual=h, what='res_block dgrad2')
-            if not masked:
-                _conv(gout, w2, gh, transposed=True, what='res_block dgrad2')
-            hmask = None if masked else h
-            if need_w1 or need_b1:
-                gw1 = _pgrad(w1)
-                gb1 = _pgrad(ctx.bias_p[0]) if ctx.has_bias[0] else None
-                _conv_wgrad(x, gh, gw1, gb1, gact=hmask, what='res_block wgrad1')
-            if need_x:
-                gx = torch.empty_like(x)
-                _conv(gh, w1, gx, transposed=True, xact=hmask, residual=gout, what='res_block dgrad1')
-        return gx, gw1, gb1, gw2, gb2
+        return _res_chain_backward('res_block', gout, gout, x, h, w1, ctx.bias_p[0], w2, ctx.bias_p[1], ctx.needs_input_grad)
 
 
 class _ConvCatBcast(Function):
@@ -899,7 +909,6 @@ class _TSATemporalBlock(Function):
         _lib.check(_lib.lib().rvsr_tsa_temporal_forward(_p(emb), _p(emb_ref), _p(aligned), _p(mod), _p(prob), B, N, C, H, W, 1, _stream()),
                    'tsa_temporal_forward')
         ctx.center = center
-        ctx.has_bias = (b1 is not None, b2 is not None)
         ctx.bias_p = (b1, b2)   # only to find their gradient buffers (_pgrad)
         ctx.save_for_backward(aligned, emb, emb_ref, prob, w1, w2)
         return mod
@@ -916,13 +925,9 @@ class _TSATemporalBlock(Function):
                                                          _p(gemb_ref), B, N, C, H, W, 1, _stream()), 'tsa_temporal_backward')
         gw1 = gb1 = gw2 = gb2 = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            gw1 = _pgrad(w1)
-            gb1 = _pgrad(ctx.bias_p[0]) if ctx.has_bias[0] else None
-            _conv_wgrad(aligned, gemb, gw1, gb1, what='tsa wgrad tAtt_1')
+            gw1, gb1 = _wgrad(aligned, gemb, w1, ctx.bias_p[0], what='tsa wgrad tAtt_1')
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
-            gw2 = _pgrad(w2)
-            gb2 = _pgrad(ctx.bias_p[1]) if ctx.has_bias[1] else None
-            _conv_wgrad(aligned[center], gemb_ref, gw2, gb2, what='tsa wgrad tAtt_2')
+            gw2, gb2 = _wgrad(aligned[center], gemb_ref, w2, ctx.bias_p[1], what='tsa wgrad tAtt_2')
         if ctx.needs_input_grad[0]:
             # galigned += dgrad(tAtt_1)(gemb), in place: the kernel's fused residual is its own output buffer (every lane reads
             # the residual values of exactly the addresses it then stores)
@@ -1024,17 +1029,28 @@ def pyr_updiff(cur, down):
     return _PyrUpDiff.apply(cur, down)
 
 
+def _reduce_workspace(device):
+    return _workspace(_lib.lib().rvsr_reduce_workspace_bytes(), device)
+
+
+def _scalar_loss(x, n, mean=True):
+    """What a scalar-loss forward starts from: the 0-d output, the reduction workspace, and the scale of the sum (1 / n for a mean)."""
+    return x.new_empty(()), _reduce_workspace(x.device), (1.0 / n if mean else 1.0)
+
+
+def _pair_grads(ctx, gx):
+    """(gx, gy) of a loss of x - y: the second operand's gradient is the negated first, formed only when wanted."""
+    return gx, (-gx if ctx.needs_input_grad[1] else None)
+
+
 class _Charbonnier(Function):
     @staticmethod
     def forward(ctx, x, y, eps, mean):
         _need_cuda(x, y)
         x, y = x.contiguous(), y.contiguous()
         n = x.numel()
-        out = x.new_empty(())
-        L = _lib.lib()
-        ws = _workspace(L.rvsr_charbonnier_workspace_bytes(), x.device)
-        scale = 1.0 / n if mean else 1.0
-        _lib.check(L.rvsr_charbonnier_forward(_p(x), _p(y), n, eps, scale, _p(out), _p(ws), _stream()),
+        out, ws, scale = _scalar_loss(x, n, mean)
+        _lib.check(_lib.lib().rvsr_charbonnier_forward(_p(x), _p(y), n, eps, scale, _p(out), _p(ws), _stream()),
                    'charbonnier_forward')
         ctx.cfg = (eps, scale)
         ctx.save_for_backward(x, y)
@@ -1049,8 +1065,7 @@ class _Charbonnier(Function):
         gx = torch.empty_like(x)
         _lib.check(_lib.lib().rvsr_charbonnier_backward(_p(x), _p(y), _p(g), scale, eps, _p(gx), x.numel(), _stream()),
                    'charbonnier_backward')
-        gy = -gx if ctx.needs_input_grad[1] else None
-        return gx, gy, None, None
+        return (*_pair_grads(ctx, gx), None, None)
 
 
 def charbonnier(x, y, eps=1e-6, reduction='mean'):
@@ -1063,14 +1078,10 @@ class _GWLoss(Function):
         _need_cuda(x1, x2)
         x1, x2 = x1.contiguous(), x2.contiguous()
         B, C, H, W = x1.shape
-        n = x1.numel()
-        out = x1.new_empty(())
-        L = _lib.lib()
-        ws = _workspace(L.rvsr_charbonnier_workspace_bytes(), x1.device)
-        scale = 1.0 / n if mean else 1.0
+        out, ws, scale = _scalar_loss(x1, x1.numel(), mean)
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         fac = x1.new_empty(3, B, C, H, W) if need else None
-        _lib.check(L.rvsr_gwloss_forward(_p(x1), _p(x2), B * C, H, W, float(w), scale, _p(out),
+        _lib.check(_lib.lib().rvsr_gwloss_forward(_p(x1), _p(x2), B * C, H, W, float(w), scale, _p(out),
                                          _p(fac[0]) if need else None, _p(fac[1]) if need else None,
                                          _p(fac[2]) if need else None, _p(ws), _stream()), 'gwloss_forward')
         ctx.cfg = (scale, B, C, H, W)
@@ -1086,7 +1097,7 @@ class _GWLoss(Function):
         gx = fac.new_empty(B, C, H, W)
         _lib.check(_lib.lib().rvsr_gwloss_backward(_p(fac[0]), _p(fac[1]), _p(fac[2]), _p(g), scale, _p(gx), B * C, H, W,
                                                    _stream()), 'gwloss_backward')
-        return gx, (-gx if ctx.needs_input_grad[1] else None), None, None
+        return (*_pair_grads(ctx, gx), None, None)
 
 
 def gw_loss(x1, x2, w=4, reduction='mean'):
@@ -1104,11 +1115,8 @@ class _PixelLoss(Function):
             raise RuntimeError('pixel loss: shapes %s and %s differ' % (tuple(x.shape), tuple(y.shape)))
         x, y = x.contiguous(), y.contiguous()
         n = x.numel()
-        out = x.new_empty(())
-        L = _lib.lib()
-        ws = _workspace(L.rvsr_reduce_workspace_bytes(), x.device)
-        scale = 1.0 / n if mean else 1.0
-        _lib.check(L.rvsr_pixel_loss_forward(_p(x), _p(y), n, mode, param, scale, _p(out), _p(ws), _stream()),
+        out, ws, scale = _scalar_loss(x, n, mean)
+        _lib.check(_lib.lib().rvsr_pixel_loss_forward(_p(x), _p(y), n, mode, param, scale, _p(out), _p(ws), _stream()),
                    'pixel_loss_forward')
         ctx.cfg = (mode, param, scale)
         ctx.save_for_backward(x, y)
@@ -1123,7 +1131,7 @@ class _PixelLoss(Function):
         gx = torch.empty_like(x)
         _lib.check(_lib.lib().rvsr_pixel_loss_backward(_p(x), _p(y), _p(g), mode, param, scale, _p(gx), x.numel(),
                                                        _stream()), 'pixel_loss_backward')
-        return gx, (-gx if ctx.needs_input_grad[1] else None), None, None, None
+        return (*_pair_grads(ctx, gx), None, None, None)
 
 
 PIX_L1, PIX_L2, PIX_HUBER, PIX_CHARBONNIER = 0, 1, 2, 3
@@ -1144,13 +1152,10 @@ class _SSIMLoss(Function):
             raise RuntimeError('ssim: expected two equal (B, C, H, W) tensors, got %s and %s' % (tuple(x.shape), tuple(y.shape)))
         x, y = x.contiguous(), y.contiguous()
         B, C, H, W = x.shape
-        out = x.new_empty(())
-        L = _lib.lib()
-        ws = _workspace(L.rvsr_reduce_workspace_bytes(), x.device)
+        out, ws, scale = _scalar_loss(x, max(B * C * (H - 10) * (W - 10), 1))
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         maps = x.new_empty(3, B * C, H - 10, W - 10) if need and H > 10 and W > 10 else None
-        scale = 1.0 / max(B * C * (H - 10) * (W - 10), 1)
-        _lib.check(L.rvsr_ssim_forward(_p(x), _p(y), B * C, H, W, scale, _p(out),
+        _lib.check(_lib.lib().rvsr_ssim_forward(_p(x), _p(y), B * C, H, W, scale, _p(out),
                                        _p(maps[0]) if maps is not None else None,
                                        _p(maps[1]) if maps is not None else None,
                                        _p(maps[2]) if maps is not None else None, _p(ws), _stream()), 'ssim_forward')
@@ -1172,9 +1177,8 @@ class _SSIMLoss(Function):
                                             planes, H, W, _stream()), 'ssim_backward')
         if ctx.needs_input_grad[1]:
             # SSIM is symmetric: the derivative maps w.r.t. the second image are those of ssim(y, x)
-            tmp = x.new_empty(())
+            tmp, ws, _ = _scalar_loss(x, 1)
             m2 = torch.empty_like(maps)
-            ws = _workspace(L.rvsr_reduce_workspace_bytes(), x.device)
             _lib.check(L.rvsr_ssim_forward(_p(y), _p(x), planes, H, W, scale, _p(tmp), _p(m2[0]), _p(m2[1]), _p(m2[2]),
                                            _p(ws), _stream()), 'ssim_forward (swapped)')
             gy = torch.empty_like(y)
@@ -1457,7 +1461,6 @@ class _RCABFused(Function):
         out, pooled, hidden, gate = _ca_forward(u, x, wd, bd, wu, bu, res_scale)
         ctx.save_for_backward(x, h, u, w1, w2, wd, wu, pooled, hidden, gate)
         ctx.res_scale = res_scale
-        ctx.has_bias = (b1 is not None, b2 is not None)
         ctx.params = (b1, b2, wd, bd, wu, bu)   # only to find their gradient buffers (_pgrad)
         return out
 
@@ -1468,31 +1471,11 @@ class _RCABFused(Function):
         b1, b2, wd_p, bd_p, wu_p, bu_p = ctx.params
         gout = gout.contiguous()
         need = ctx.needs_input_grad
-        need_x, need_w1, need_b1, need_w2, need_b2 = need[:5]
-        gx = gw1 = gb1 = gw2 = gb2 = None
         if not any(need[:9]):
             return (None,) * 10
         gca = [_pgrad(p) if need[5 + i] else None for i, p in enumerate((wd_p, bd_p, wu_p, bu_p))]
-        gu =_ca_backward(gout, u, wd, wu, pooled, hidden, gate, ctx.res_scale, *gca)
-        if need_w2 or need_b2:
-            gw2 = _pgrad(w2)
-            gb2 = _pgrad(b2) if ctx.has_bias[1] else None
-            _conv_wgrad(h, gu, gw2, gb2, what='rcab wgrad2')
-        if need_x or need_w1 or need_b1:
-            # as in _ResBlockFused: relu'(h) in the epilogue of conv2's data gradient where the plan grants it, else in the two consumers
-            gh = torch.empty_like(x)
-            masked = _FUSE_GRAD_MASK and _conv(gu, w2, gh, transposed=True, act=ACT_MASK, residual=h, what='rcab dgrad2')
-            if not masked:
-                _conv(gu, w2, gh, transposed=True, what='rcab dgrad2')
-            hmask = None if masked else h
-            if need_w1 or need_b1:
-                gw1 = _pgrad(w1)
-                gb1 = _pgrad(b1) if ctx.has_bias[0] else None
-                _conv_wgrad(x, gh, gw1, gb1, gact=hmask, what='rcab wgrad1')
-            if need_x:
-                gx = torch.empty_like(x)
-                _conv(gh, w1, gx, transposed=True, xact=hmask, residual=gout, what='rcab dgrad1')
-        return gx, gw1, gb1, gw2, gb2, gca[0], gca[1], gca[2], gca[3], None
+        gu = _ca_backward(gout, u, wd, wu, pooled, hidden, gate, ctx.res_scale, *gca)
+        return (*_res_chain_backward('rcab', gu, gout, x, h, w1, b1, w2, b2, need[:5]), *gca, None)
 
 
 def rcab(x, conv1, conv2, conv_down, conv_up, res_scale=1.0):
@@ -1505,6 +1488,21 @@ def rcab(x, conv1, conv2, conv_down, conv_up, res_scale=1.0):
 # Activations are FRAME-MAJOR, [T, B, C, H, W] contiguous: a range of frames is a contiguous batch for the [..., C, H, W] kernels above, and
 # the three temporal taps of a pixel are three pointers one frame apart (csrc/conv3d_kernels.hip).
 _FUSE_TCONV3 = True   # off: the (3,1,1) convolution composed from three 1x1 convs over frame ranges -- the fallback and the yardstick
+
+
+def _c3_wgrad(x, gout, weight, bias, taps, what):
+    """(gw, gb) of a kernel-3-in-time convolution with weight (Co, Ci, 3, k, k), into the parameters' gradient buffers: the 2-D
+    weight-gradient kernel once per tap over the frame range the tap meets (deterministic partial sums), scattered into the dt slices.
+    The first tap covers every output frame and carries the bias gradient; a tap that meets no frame (T == 1) gets zeros."""
+    gw = _pgrad(weight)
+    gb = _pgrad(bias) if bias is not None else None
+    tmp = gw.new_empty(gw.shape[0], gw.shape[1], *gw.shape[3:])
+    for i, (dt, a, n, o) in enumerate(taps):
+        _conv_wgrad(x[a:a + n], gout[o:o + n], tmp, gb if i == 0 else None, what=what)
+        gw[:, :, dt].copy_(tmp)
+    for dt in set(range(3)) - {t[0] for t in taps}:
+        gw[:, :, dt].zero_()
+    return gw, gb
 
 
 def _c3_taps(T, f0, f1):
@@ -1560,16 +1558,7 @@ class _Conv3dFrames(Function):
                 dst = gx[a:a + n]
                 _conv(gout[o:o + n], wdt[dt], dst, transposed=True, residual=None if i == 0 else dst, what='conv3d_frames dgrad')
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            gw = _pgrad(weight)
-            gb = _pgrad(bias) if has_bias else None
-            tmp = torch.empty_like(wdt[0])
-            done = set()
-            for i, (dt, a, n, o) in enumerate(taps):
-                _conv_wgrad(x[a:a + n], gout[o:o + n], tmp, gb if i == 0 else None, what='conv3d_frames wgrad')
-                gw[:, :, dt].copy_(tmp)
-                done.add(dt)
-            for dt in set(range(3)) - done:   # (a tap that meets no frame: T == 1)
-                gw[:, :, dt].zero_()
+            gw, gb = _c3_wgrad(x, gout, weight, bias, taps, 'conv3d_frames wgrad')
         return gx, gw, gb, (gout if has_res else None), None, None
 
 
@@ -1672,18 +1661,9 @@ def _tconv3_run(s, w, bias=None, residual=None, slope=None, transposed=False):
     return out, pout
 
 
-def _tconv3_wgrad(s, gout, gw, gb):
-    """Weight gradient (Co, Ci, 3, 1, 1) and bias gradient of the temporal convolution: the 1x1 weight-gradient kernel once per tap over
-    the frame range the tap meets (deterministic partial sums), scattered into the dt slices."""
-    T = s.shape[0]
-    tmp = gw.new_empty(gw.shape[0], gw.shape[1], 1, 1)
-    done = set()
-    for i, (dt, a, n, o) in enumerate(_c3_taps(T, 0, T)):
-        _conv_wgrad(s[a:a + n], gout[o:o + n], tmp, gb if i == 0 else None, what='tconv3 wgrad')
-        gw[:, :, dt].copy_(tmp)
-        done.add(dt)
-    for dt in set(range(3)) - done:
-        gw[:, :, dt].zero_()
+def _tconv3_wgrad(s, gout, weight, bias):
+    """(gw, gb) of the temporal convolution with weight (Co, Ci, 3, 1, 1): _c3_wgrad over all frames with the 1x1 kernel."""
+    return _c3_wgrad(s, gout, weight, bias, _c3_taps(s.shape[0], 0, s.shape[0]), 'tconv3 wgrad')
 
 
 class _TConv3(Function):
@@ -1717,9 +1697,7 @@ class _TConv3(Function):
         if need[0]:
             gs, _ = _tconv3_run(g, weight, transposed=True)
         if need[1] or (has_bias and need[2]):
-            gw = _pgrad(weight_p)
-            gb = _pgrad(bias_p) if has_bias else None
-            _tconv3_wgrad(s, g, gw, gb)
+            gw, gb = _tconv3_wgrad(s, g, weight_p, bias_p)
         return gs, gw, gb, (g if has_res and need[3] else None), gslope
 
 
@@ -1770,17 +1748,13 @@ class _FRBFused(Function):
             g = _prelu_backward(gpout.contiguous(), out, None, next_slope, gres=g, gslope=gnext)
         gw1 = gb1 = gw2 = gb2 = gslope = gx = gpx = None
         if need[5] or need[6]:   # (the weight-gradient kernels produce weight and bias gradient in one call, as in the conv nodes above)
-            gw2 = _pgrad(w2_p)
-            gb2 = _pgrad(b2_p) if b2_p is not None else None
-            _tconv3_wgrad(h, g, gw2, gb2)
+            gw2, gb2 = _tconv3_wgrad(h, g, w2_p, b2_p)
         # what lies below conv3d_2: the gradient of px, wanted by this block's own PReLU (for x or the slope) or by the previous block's node
         need_gpx = (need[0] or need[2]) if ctx.own else need[1]
         if need[3] or need[4] or need_gpx:
             gh, _ = _tconv3_run(g, w2, transposed=True)
             if need[3] or need[4]:
-                gw1 = _pgrad(w1_p)
-                gb1 = _pgrad(b1_p) if b1_p is not None else None
-                _conv_wgrad(px, gh, gw1[:, :, 0], gb1, what='frb wgrad1')
+                gw1, gb1 = _wgrad(px, gh, w1_p, b1_p, what='frb wgrad1')   # ((C, C, 1, 3, 3): the 2-D layout)
             if need_gpx:
                 gpx = torch.empty_like(px)
                 _conv(gh, w1[:, :, 0], gpx, transposed=True, what='frb dgrad1')

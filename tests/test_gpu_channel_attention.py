@@ -173,16 +173,17 @@ def test_refusals():
         RF.channel_attention(u.double(), torch.nn.Conv2d(16, 1, 1).to(d).double(), torch.nn.Conv2d(1, 16, 1).to(d).double())
 
 
-def test_rcab_node_vs_composed(gemm_mode):
+def _rcab_case(gemm_mode, C, B, H, W, frozen=()):
     """rcab(...) as one autograd node against the same block composed from RF.conv2d + channel_attention + x: output, gx and all
-    eight parameter gradients.  Both sides run the same conv kernels: the tolerances of the running GEMM mode."""
+    eight parameter gradients.  Both sides run the same conv kernels: the tolerances of the running GEMM mode.  The inputs named in
+    `frozen` ('x', 'conv1', 'conv2': both parameters of the conv) require no gradient in the node's run and must get None."""
     from realvsr_amd import functional as RF
     T, T_G, _ = TOLS[gemm_mode]
     d = dev()
     gen = torch.Generator().manual_seed(9)
-    C, r = 64, 16
-    x0 = torch.randn(2, C, 12, 20, generator=gen).to(d)
-    g = torch.randn(2, C, 12, 20, generator=gen).to(d)
+    r = 16
+    x0 = torch.randn(B, C, H, W, generator=gen).to(d)
+    g = torch.randn(B, C, H, W, generator=gen).to(d)
     mods = [torch.nn.Conv2d(C, C, 3, 1, 1), torch.nn.Conv2d(C, C, 3, 1, 1), torch.nn.Conv2d(C, C // r, 1), torch.nn.Conv2d(C // r, C, 1)]
     with torch.no_grad():
         for m in mods:
@@ -193,9 +194,10 @@ def test_rcab_node_vs_composed(gemm_mode):
     c1, c2, down, up = mods
 
     def run(fused):
-        for m in mods:
+        for m, n in zip(mods, ('conv1', 'conv2', 'down', 'up')):
             m.zero_grad(set_to_none=True)
-        x = x0.detach().requires_grad_(True)
+            m.requires_grad_(not (fused and n in frozen))
+        x = x0.detach().requires_grad_(not (fused and 'x' in frozen))
         if fused:
             y = RF.rcab(x, c1, c2, down, up, 0.5)
         else:
@@ -207,4 +209,18 @@ def test_rcab_node_vs_composed(gemm_mode):
     check('out', got[0], want[0], T)
     names = ['gx'] + ['g%s.%s' % (n, k) for n in ('conv1', 'conv2', 'down', 'up') for k in ('weight', 'bias')]
     for name, a, b in zip(names, got[1:], want[1:]):
-        gcheck(gemm_mode, name, a, b, T_G)
+        if name.split('.')[0][1:] in frozen:      # 'gx' -> 'x', 'gconv1.weight' -> 'conv1'
+            assert a is None, name
+        else:
+            gcheck(gemm_mode, name, a, b, T_G)
+
+
+def test_rcab_node_vs_composed(gemm_mode):
+    _rcab_case(gemm_mode, 64, 2, 12, 20)
+
+
+@pytest.mark.parametrize('frozen', ['x', 'conv1', 'conv2'])
+def test_rcab_frozen_inputs_vs_composed(frozen, gemm_mode):
+    """needs_input_grad of the node, as test_gpu_conv_nodes.test_res_block_frozen_inputs_vs_float64: the chain behind the channel
+    attention skips conv1's data gradient, conv1's or conv2's weight gradient; what is still wanted is what it was."""
+    _rcab_case(gemm_mode, 16, 1, 8, 12, (frozen,))

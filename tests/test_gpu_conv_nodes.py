@@ -100,9 +100,9 @@ def test_frames_of_the_mask_epilogue(gemm_mode):
         assert RF.grad_mask_fusable(H, W) is False, (H, W)
 
 
-@pytest.mark.parametrize('geo', RES_BLOCKS, ids=_ids(RES_BLOCKS))
-def test_res_block_vs_float64(geo, gemm_mode):
-    """x + conv2(relu(conv1(x))): the output and all five gradients."""
+def _res_block_case(geo, gemm_mode, frozen=()):
+    """x + conv2(relu(conv1(x))) against float64: the output and the five gradients; those of the inputs named in `frozen` (of x, w1,
+    b1, w2, b2), which do not require one, must be None."""
     from realvsr_amd import functional as RF
     TOL = TOLS[gemm_mode]
     C, B, H, W = geo
@@ -119,16 +119,36 @@ def test_res_block_vs_float64(geo, gemm_mode):
 
     d = dev()
     c1, c2 = _holder(w1, b1, d), _holder(w2, b2, d)
-    xg = x.to(d).requires_grad_(True)
+    xg = x.to(d)
+    leaves = {'x': xg, 'w1': c1.weight, 'b1': c1.bias, 'w2': c2.weight, 'b2': c2.bias}
+    for k, t in leaves.items():
+        t.requires_grad_(k not in frozen)
     y = RF.res_block(xg, c1, c2)
     y.backward(gout.to(d))
     torch.cuda.synchronize()
     check('out', y, yr, TOL)
-    check('grad_w2', c2.weight.grad, r[3].grad, TOL)
-    check('grad_b2', c2.bias.grad, r[4].grad, TOL)
-    check('grad_x', xg.grad, r[0].grad, 2 * TOL)
-    check('grad_w1', c1.weight.grad, r[1].grad, 2 * TOL)
-    check('grad_b1', c1.bias.grad, r[2].grad, 2 * TOL)
+    for k, ref, tol in (('w2', r[3], TOL), ('b2', r[4], TOL), ('x', r[0], 2 * TOL), ('w1', r[1], 2 * TOL), ('b1', r[2], 2 * TOL)):
+        if k in frozen:
+            assert leaves[k].grad is None, k
+        else:
+            check('grad_' + k, leaves[k].grad, ref.grad, tol)
+
+
+@pytest.mark.parametrize('geo', RES_BLOCKS, ids=_ids(RES_BLOCKS))
+def test_res_block_vs_float64(geo, gemm_mode):
+    """x + conv2(relu(conv1(x))): the output and all five gradients."""
+    _res_block_case(geo, gemm_mode)
+
+
+# which inputs of a conv1 + ReLU, conv2 node need no gradient: the backward chain of res_block and rcab skips what only they need
+FROZEN = {'x': ('x',), 'conv1': ('w1', 'b1'), 'conv2': ('w2', 'b2')}
+
+
+@pytest.mark.parametrize('frozen', list(FROZEN))
+def test_res_block_frozen_inputs_vs_float64(frozen, gemm_mode):
+    """needs_input_grad of the node: x without a gradient (no dgrad1), conv1 frozen (no wgrad1), conv2 frozen (no wgrad2); the
+    gradients still wanted are what they were, the others None."""
+    _res_block_case((16, 1, 8, 12), gemm_mode, FROZEN[frozen])
 
 
 def _bcast_ref(x, ref, w, b, N, act, slope):

@@ -50,9 +50,8 @@ def tconv3_times(T, B, S, reps, rounds=2):
     conv = torch.nn.Conv3d(C, C, (3, 1, 1), padding=(1, 0, 0)).to(d)
     act = torch.nn.PReLU().to(d)
     w, b, sl = conv.weight.detach(), conv.bias.detach(), act.weight.detach()
-    gw, gb = torch.empty_like(w), torch.empty_like(b)
     calls = {'fwd': lambda: RF._tconv3_run(s, w, b, res, sl), 'dgrad': lambda: RF._tconv3_run(gout, w, transposed=True),
-             'wgrad': lambda: RF._tconv3_wgrad(s, gout, gw, gb)}
+             'wgrad': lambda: RF._tconv3_wgrad(s, gout, w, b)}
     samples = {}
     was = RF._FUSE_TCONV3
     try:
