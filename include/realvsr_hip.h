@@ -40,6 +40,11 @@ extern "C" {
 #define RVSR_ERR_LAUNCH 3      /* HIP launch error                                                */
 #define RVSR_ERR_WORKSPACE 4   /* workspace missing or too small                                  */
 
+/* In front of a parameter: a pointer into HOST memory that the call writes through.  Every unmarked pointer is device memory, or a
+ * buffer whose comment says where it lives.  (realvsr_amd/_lib.py reads its ctypes signatures from this file: a marked int* / long long*
+ * is a typed POINTER there, every other pointer a void*.) */
+#define RVSR_HOST
+
 const char* rvsr_last_error(void);
 
 /* GEMM arithmetic of the conv blocks: 0 (default) = 3-term bf16 split on the bf16 matrix cores
@@ -160,7 +165,7 @@ int rvsr_deform_conv_backward_parameters(const float* input, const float* offset
  * from an earlier statistic, rvsr_dcn_offset_probe), else 3 px; out-of-tile samples gather from global memory in every case. */
 int rvsr_dcn_offset_probe(const float* om, int batch, int height_out, int width_out, int deformable_group, void* probe, void* stream);
 size_t rvsr_dcn_pack_weights(const float* weight, int channels, int channels_out, void* out, size_t out_bytes,
-                             long long* desc, void* stream);
+                             RVSR_HOST long long* desc, void* stream);
 int rvsr_dcn_pack_forward(const float* input, const float* weight, const float* bias, const float* om,
                           float* output, int batch, int channels, int height, int width, int channels_out,
                           int stride, int pad, int dilation, int deformable_group, int act, float slope,
@@ -187,16 +192,16 @@ int rvsr_dcn_pack_backward(const float* input, const float* weight, const float*
 int rvsr_dcn_pack_forward_plan(const float* input, const float* weight, const float* bias, const float* om,
                                float* output, int batch, int channels, int height, int width, int channels_out,
                                int stride, int pad, int dilation, int deformable_group, int act, float slope,
-                               void* probe, void* workspace, size_t workspace_bytes, long long* plan);
+                               void* probe, void* workspace, size_t workspace_bytes, RVSR_HOST long long* plan);
 int rvsr_dcn_pack_backward_plan(const float* input, const float* weight, const float* om, const float* grad_output,
                                 const float* act_out, float act_slope, float* grad_input, float* grad_weight,
                                 float* grad_bias, float* grad_om, int batch, int channels, int height, int width,
                                 int channels_out, int stride, int pad, int dilation, int deformable_group,
-                                const void* probe, void* workspace, size_t workspace_bytes, long long* plan);
+                                const void* probe, void* workspace, size_t workspace_bytes, RVSR_HOST long long* plan);
 /* Three rules of csrc/dcn_plan.h for the host glue (no GPU needed): the code with which the fused entries of sections 1 / 1b answer a
  * geometry (RVSR_OK: taken); the number of samples behind the counters of rvsr_dcn_offset_probe; and the tile halo (3 / 7 / 11; 0: no
  * samples) that a forward with channels_out output channels selects on the device from such counters -- `counters`: 6 uint32 in HOST
- * memory -- so that a caller who kept them can pass the same choice as the hint of a later step. */
+ * memory, read only and therefore unmarked (RVSR_HOST) -- so that a caller who kept them can pass the same choice as the hint of a later step. */
 int rvsr_dcn_fused_takes(int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w, int stride_h,
                          int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int group, int deformable_group);
 size_t rvsr_dcn_probe_samples(int batch, int deformable_group, int height_out, int width_out);
@@ -286,7 +291,8 @@ int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const 
 int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
                              int in_mode, int Hs, int Ws, const float* weight, const float* bias,
                              const float* residual, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
-                             int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout, int* plan);
+                             int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout,
+                             RVSR_HOST int* plan);
 
 /* 2b. Packed weight images, once per optimizer step.  The matrix-core kernels stage weights as bf16 hi/lo images
  *   ([m-block][chunk][hi|lo][tap][octet][row][8]); rvsr_conv2d_forward builds that image in its workspace on every call.
@@ -303,7 +309,7 @@ int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, c
  *   {const float* w; void* out; int Co, C_in, taps, MP, CCG, nchunks, nmb, mode;} built from those descriptors: the host
  *   (realvsr_amd.caches.PackedWeights) calls it once after the optimizer has updated the parameters in place. */
 size_t rvsr_conv2d_pack_weights(const float* weight, int C_in, int Co, int ksize, int w_mode, void* out, size_t out_bytes,
-                                long long* desc, void* stream);
+                                RVSR_HOST long long* desc, void* stream);
 int rvsr_pack_weights_batched(const void* descs, int n, void* stream);
 
 /* grad_weight (Co,C1+C2,k,k) and grad_bias (Co) (NULL = skip) of the conv above.
@@ -331,7 +337,7 @@ int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2
 int rvsr_conv2d_backward_weight_plan(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
                                      const float* gout, const float* gact, float gact_slope, int g_mode,
                                      int Gs_h, int Gs_w, float* grad_weight, int Co, int B, int ksize, int stride,
-                                     int Hout, int Wout, int* plan);
+                                     int Hout, int Wout, RVSR_HOST int* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * 3. Fusion / resampling element-wise chain
@@ -518,7 +524,8 @@ size_t rvsr_channel_attention_workspace_bytes(int B, int C, int H, int W);
  * tested for alignment): *slices = workgroups and partial sums per (b, c) plane -- 1 where B * C planes fill the chip, more for a few
  * planes of a large frame; *vec = 1 when the kernels use 16-byte loads and stores (H * W % 4 == 0 and all three addresses 16-byte
  * aligned; x may be NULL), else 0, the scalar path.  Either output pointer may be NULL. */
-int rvsr_channel_attention_plan(int B, int C, int H, int W, const void* u, const void* x, const void* out, int* slices, int* vec);
+int rvsr_channel_attention_plan(int B, int C, int H, int W, const void* u, const void* x, const void* out,
+                                RVSR_HOST int* slices, RVSR_HOST int* vec);
 int rvsr_channel_attention_forward(const float* u, const float* x /*NULL ok*/, const float* w1, const float* b1, const float* w2,
                                    const float* b2, float* out, float* pooled, float* hidden, float* gate, int B, int C, int Cr, int H,
                                    int W, float res_scale, void* ws, size_t ws_bytes, void* stream);
@@ -555,7 +562,7 @@ int rvsr_tconv3_forward(const float* s, const float* w, const float* bias /*NULL
  * loads and stores (H * W % 4 == 0 and s, residual, out and pout 16-byte aligned, NULL counting as aligned), else 0, the scalar path;
  * *grid = workgroups launched.  Returns what rvsr_tconv3_forward would return for the shape.  Either output pointer may be NULL. */
 int rvsr_tconv3_plan(int T, int B, int Ci, int Co, int H, int W, const void* s, const void* residual, const void* out, const void* pout,
-                     int* vec, int* grid);
+                     RVSR_HOST int* vec, RVSR_HOST int* grid);
 
 /* nn.PReLU() with one learnable slope (FSTRN_arch.py:15, :42), the long skip `lr_res + out` (:60) and nn.Dropout (:43, :62) in one pass
  * over n contiguous floats:
@@ -576,8 +583,8 @@ int rvsr_prelu_backward(const float* g, const float* a, const float* b /*NULL ok
 /* The plan of a PReLU call (pure host code): *vec as above for the f32 tensors of the call, f0 .. f4 (forward: a, b, y; backward: g, a, b,
  * gres, gx; NULL where the call has none), and the keep mask; *blocks = workgroups, which is also the number of partial sums of the slope
  * gradient.  n == 0 is RVSR_ERR_BAD_ARG. */
-int rvsr_prelu_plan(size_t n, const void* f0, const void* f1, const void* f2, const void* f3, const void* f4, const void* keep, int* vec,
-                    int* blocks);
+int rvsr_prelu_plan(size_t n, const void* f0, const void* f1, const void* f2, const void* f3, const void* f4, const void* keep,
+                    RVSR_HOST int* vec, RVSR_HOST int* blocks);
 
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);

@@ -1,112 +1,68 @@
-"""ctypes binding of librealvsr_hip.so (C ABI: include/realvsr_hip.h).
+"""ctypes binding of librealvsr_hip.so.  The C ABI is written once, in include/realvsr_hip.h: the library's sources compile against that
+header, and the ctypes signatures and the RVSR_* return codes below are parsed out of it at import (parse_header).
 
 The library is built in-tree (``realvsr_amd/csrc/librealvsr_hip.so``) by ``build()`` /
 ``__graft_entry__.build()``.  If it is missing the product fails loudly: there is no fallback.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch  # (also loads libamdhip64, which the .so links against)
 
-_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
+_PKG = os.path.dirname(os.path.abspath(__file__))
+_CSRC = os.path.join(_PKG, 'csrc')
 SO_PATH = os.environ.get('RVSR_SO', os.path.join(_CSRC, 'librealvsr_hip.so'))  # RVSR_SO: developer override for A/B builds
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), 'include', 'realvsr_hip.h')
 _lib = None
 
 c_fp = ctypes.c_void_p  # device pointers travel as void*
-c_int, c_float, c_double, c_size = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+_SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t}
+_RETURNS = dict(_SCALARS, **{'void': None, 'char*': ctypes.c_char_p})
+_POINTEES = {'void', 'float', 'int', 'long long', 'unsigned', 'unsigned char'}   # what an unmarked pointer may point at
+_HOST_OUT = {'int*': ctypes.POINTER(ctypes.c_int), 'long long*': ctypes.POINTER(ctypes.c_longlong)}   # behind the header's RVSR_HOST marker
 
-# the convolution call itself: x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, ksize,
-# stride, w_mode, act, slope, pixel_shuffle, Hout, Wout
-_CONV_CALL = [c_fp, c_int, c_fp, c_int, c_fp, c_float, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int,
-              c_int, c_int, c_int, c_float, c_int, c_int, c_int]
-# name -> (restype, argtypes); must list every symbol declared in include/realvsr_hip.h
-SIGNATURES = {
-    'rvsr_last_error': (ctypes.c_char_p, []),
-    'rvsr_modulated_deform_conv_forward': (c_int, [c_fp] * 6 + [c_int] * 16 + [c_fp, c_size, c_fp]),
-    'rvsr_modulated_deform_conv_forward_workspace_bytes': (c_size, [c_int] * 2),
-    'rvsr_modulated_deform_conv_backward_workspace_bytes': (c_size, [c_int] * 8),
-    'rvsr_modulated_deform_conv_backward': (c_int, [c_fp] * 11 + [c_int] * 16 + [c_fp, c_size, c_fp]),
-    'rvsr_deform_conv_workspace_bytes': (c_size, [c_int] * 11),
-    'rvsr_deform_conv_forward': (c_int, [c_fp] * 4 + [c_int] * 16 + [c_fp, c_size, c_fp]),
-    'rvsr_deform_conv_backward_input': (c_int, [c_fp] * 6 + [c_int] * 16 + [c_fp, c_size, c_fp]),
-    'rvsr_deform_conv_backward_parameters': (c_int, [c_fp] * 4 + [c_int] * 15 + [c_float, c_int, c_fp, c_size, c_fp]),
-    'rvsr_deform_conv_generic_workspace_bytes': (c_size, [c_int] * 12),
-    'rvsr_deform_conv_generic_forward_workspace_bytes': (c_size, [c_int] * 12),
-    'rvsr_deform_conv_generic_forward': (c_int, [c_int] + [c_fp] * 6 + [c_int] * 15 + [c_fp, c_size, c_fp]),
-    'rvsr_deform_conv_generic_backward': (c_int, [c_int] + [c_fp] * 10 + [c_int] * 15 + [c_fp, c_size, c_fp]),
-    'rvsr_dcn_pack_forward': (c_int, [c_fp] * 5 + [c_int] * 10 + [c_float, c_fp, c_fp, c_size, c_fp]),
-    'rvsr_dcn_offset_probe': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
-    'rvsr_dcn_pack_backward': (c_int, [c_fp] * 5 + [c_float] + [c_fp] * 4 + [c_int] * 9 + [c_fp, c_fp, c_size, c_fp]),
-    'rvsr_dcn_pack_forward_plan': (c_int, [c_fp] * 5 + [c_int] * 10 + [c_float, c_fp, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong)]),
-    'rvsr_dcn_pack_backward_plan': (c_int, [c_fp] * 5 + [c_float] + [c_fp] * 4 + [c_int] * 9 + [c_fp, c_fp, c_size,
-                                                                                             ctypes.POINTER(ctypes.c_longlong)]),
-    'rvsr_dcn_fused_takes': (c_int, [c_int] * 15),
-    'rvsr_dcn_probe_samples': (c_size, [c_int] * 4),
-    'rvsr_dcn_forward_halo': (c_int, [c_fp, c_size, c_int]),
-    'rvsr_conv2d_forward': (c_int, _CONV_CALL + [c_fp, c_size, c_fp]),
-    'rvsr_conv2d_forward_plan': (c_int, _CONV_CALL + [ctypes.POINTER(c_int)]),
-    'rvsr_conv2d_forward_workspace_bytes': (c_size, [c_int] * 4),
-    'rvsr_conv2d_pack_weights': (c_size, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong), c_fp]),
-    'rvsr_dcn_pack_weights': (c_size, [c_fp, c_int, c_int, c_fp, c_size, ctypes.POINTER(ctypes.c_longlong), c_fp]),
-    'rvsr_pack_weights_batched': (c_int, [c_fp, c_int, c_fp]),
-    'rvsr_set_gemm_mode': (None, [c_int]),
-    'rvsr_get_gemm_mode': (c_int, []),
-    'rvsr_set_gemm_mode_thread': (None, [c_int]),
-    'rvsr_conv2d_wgrad_workspace_bytes': (c_size, [c_int] * 8),
-    'rvsr_conv2d_backward_weight': (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_float, c_int, c_int,
-                                            c_int, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
-                                            c_size, c_fp]),
-    'rvsr_conv2d_backward_weight_plan': (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_float, c_int, c_int, c_int, c_fp] +
-                                         [c_int] * 6 + [ctypes.POINTER(c_int)]),
-    'rvsr_upsample_bilinear_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_int, c_float, c_fp]),
-    'rvsr_upsample_bilinear_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_int, c_float, c_fp]),
-    'rvsr_maxavgpool_forward': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
-    'rvsr_maxavgpool_backward': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
-    'rvsr_tsa_temporal_forward': (c_int, [c_fp] * 5 + [c_int] * 6 + [c_fp]),
-    'rvsr_tsa_temporal_backward': (c_int, [c_fp] * 8 + [c_int] * 6 + [c_fp]),
-    'rvsr_tsa_output_forward': (c_int, [c_fp] * 4 + [c_size, c_fp]),
-    'rvsr_tsa_output_backward': (c_int, [c_fp] * 5 + [c_size, c_fp]),
-    'rvsr_pyr_down_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_pyr_down_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_pyr_updiff_forward': (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_pyr_updiff_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_charbonnier_workspace_bytes': (c_size, []),
-    'rvsr_charbonnier_forward': (c_int, [c_fp, c_fp, c_size, c_float, c_double, c_fp, c_fp, c_fp]),
-    'rvsr_charbonnier_backward': (c_int, [c_fp, c_fp, c_fp, c_float, c_float, c_fp, c_size, c_fp]),
-    'rvsr_gwloss_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_float, c_double, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    'rvsr_gwloss_backward': (c_int, [c_fp, c_fp, c_fp, c_fp, c_float, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_ycbcr_to_bgr_u8': (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
-    'rvsr_reduce_workspace_bytes': (c_size, []),
-    'rvsr_pixel_loss_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_float, c_double, c_fp, c_fp, c_fp]),
-    'rvsr_pixel_loss_backward': (c_int, [c_fp, c_fp, c_fp, c_int, c_float, c_float, c_fp, c_size, c_fp]),
-    'rvsr_ssim_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_double, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    'rvsr_ssim_backward': (c_int, [c_fp] * 6 + [c_float, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_conv_gauss_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_float, c_fp]),
-    'rvsr_conv_gauss_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_float, c_fp]),
-    'rvsr_pyr_upsample_forward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_pyr_upsample_backward': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_fp]),
-    'rvsr_adam_step': (c_int, [c_fp] * 4 + [c_size] + [c_float] * 6 + [c_fp]),
-    'rvsr_bcast_add_act': (c_int, [c_fp, c_fp, c_size, c_int, c_int, c_float, c_fp]),
-    'rvsr_bcast_reduce_act': (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_float, c_fp]),
-    'rvsr_augment_clips': (c_int, [c_fp] * 5 + [c_size] + [c_int] * 10 + [c_float, c_fp]),
-    'rvsr_bn_workspace_bytes': (c_size, [c_int] * 3),
-    'rvsr_bn_lrelu_forward': (c_int, [c_fp] * 9 + [c_int] * 4 + [c_float] * 3 + [c_fp, c_size, c_fp]),
-    'rvsr_bn_lrelu_backward': (c_int, [c_fp] * 9 + [c_int] * 4 + [c_float, c_fp, c_size, c_fp]),
-    'rvsr_gan_loss_forward': (c_int, [c_fp, c_size, c_fp, c_size, c_float, c_double, c_fp, c_fp, c_fp]),
-    'rvsr_gan_loss_backward': (c_int, [c_fp, c_size, c_size, c_fp, c_fp, c_float, c_float, c_fp, c_fp, c_fp]),
-    'rvsr_channel_attention_workspace_bytes': (c_size, [c_int] * 4),
-    'rvsr_channel_attention_plan': (c_int, [c_int] * 4 + [c_fp] * 3 + [ctypes.POINTER(c_int)] * 2),
-    'rvsr_channel_attention_forward': (c_int, [c_fp] * 10 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
-    'rvsr_channel_attention_backward': (c_int, [c_fp] * 12 + [c_int] * 5 + [c_float, c_fp, c_size, c_fp]),
-    'rvsr_tconv3_plan': (c_int, [c_int] * 6 + [c_fp] * 4 + [ctypes.POINTER(c_int)] * 2),
-    'rvsr_tconv3_forward': (c_int, [c_fp] * 7 + [c_int] * 7 + [c_fp]),
-    'rvsr_prelu_workspace_bytes': (c_size, []),
-    'rvsr_prelu_plan': (c_int, [c_size] + [c_fp] * 6 + [ctypes.POINTER(c_int)] * 2),
-    'rvsr_prelu_forward': (c_int, [c_fp] * 4 + [c_float, c_fp, c_size, c_fp]),
-    'rvsr_prelu_backward': (c_int, [c_fp] * 5 + [c_float, c_fp, c_fp, c_fp, c_size, c_fp, c_size, c_fp]),
-    'rvsr_debug_mfma_rate': (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
-}
+
+def parse_header(text):
+    """The text of a C header -> ({entry: (restype, argtypes)}, {RVSR_* macro: int}).  Every statement has to be a prototype
+    `ret name(type arg, ...);` over the types above: anything else raises, naming the entry -- no prototype is skipped."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    codes = {k: int(v, 0) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(RVSR_\w+)[ \t]+(-?\w+)[ \t]*$', text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$|extern\s*"C"\s*\{|\}', ' ', text, flags=re.M)
+
+    def norm(t):
+        return re.sub(r'\s*\*', '*', ' '.join(re.sub(r'\bconst\b', ' ', t).split()))
+
+    signatures = {}
+    for stmt in filter(None, (' '.join(s.split()) for s in text.split(';'))):
+        m = re.fullmatch(r'([\w\s*]+?)\b(\w+) ?\(([^()]*)\)', stmt)
+        if not m:
+            raise ValueError('C ABI header: cannot read the statement %r' % stmt)
+        ret, name, params = norm(m.group(1)), m.group(2), m.group(3).strip()
+        if name in signatures:
+            raise ValueError('C ABI header: %s is declared twice' % name)
+        if ret not in _RETURNS:
+            raise ValueError('C ABI header: %s returns the unmapped type %r' % (name, ret))
+        argtypes = []
+        for param in ([] if params in ('', 'void') else params.split(',')):
+            pm = re.fullmatch(r'\s*(RVSR_HOST\b)?(.+?)\b\w+\s*', param)
+            t = norm(pm.group(2)) if pm else None
+            if pm and pm.group(1) and t in _HOST_OUT:
+                argtypes.append(_HOST_OUT[t])
+            elif pm and not pm.group(1) and t in _SCALARS:
+                argtypes.append(_SCALARS[t])
+            elif pm and not pm.group(1) and t.endswith('*') and t[:-1] in _POINTEES:
+                argtypes.append(c_fp)
+            else:
+                raise ValueError('C ABI header: %s has the unmapped parameter %r' % (name, ' '.join(param.split())))
+        signatures[name] = (_RETURNS[ret], argtypes)
+    return signatures, codes
+
+
+with open(HEADER_PATH) as _f:
+    SIGNATURES, _codes = parse_header(_f.read())   # name -> (restype, argtypes) of every entry point the header declares
+globals().update(_codes)   # RVSR_OK, RVSR_ERR_UNSUPPORTED, ...
 
 
 def _p(t):
@@ -137,7 +93,7 @@ def lib():
                 '(or `make -C realvsr_amd/csrc`).  There is no CPU / eager fallback.' % SO_PATH)
         handle = ctypes.CDLL(SO_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the header and the library disagree
+            fn = getattr(handle, name)  # AttributeError if the library lacks an entry point the header declares
             fn.restype = res
             fn.argtypes = args
         mode = os.environ.get('RVSR_GEMM', 'bf16x3')

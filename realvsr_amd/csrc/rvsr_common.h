@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/realvsr_hip.h"  // the C ABI: every entry point's definition is compiled against its prototype; RVSR_OK / RVSR_ERR_*
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -149,12 +150,7 @@ __device__ __forceinline__ float tcat_get(const TCat& t, int bidx, int c, int y,
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side error plumbing (FAIL below; rvsr_last_error and the string itself: misc_kernels.hip)
-#define RVSR_OK 0
-#define RVSR_ERR_UNSUPPORTED 1
-#define RVSR_ERR_BAD_ARG 2
-#define RVSR_ERR_LAUNCH 3
-#define RVSR_ERR_WORKSPACE 4
+// host-side error plumbing (FAIL below with the header's RVSR_ERR_* codes; rvsr_last_error and the string itself: misc_kernels.hip)
 
 // dst[i] (+)= sum_q part[q][i], q < P: 64 elements per block, 4 thread groups stride over the
 // partials (fixed order -> run-to-run deterministic), combined through LDS.  A second segment (the bias partials of

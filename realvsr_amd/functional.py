@@ -156,7 +156,7 @@ def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode
     else:
         ws = _workspace(nbytes, torch.device('cuda', torch.cuda.current_device()))
     rc = L.rvsr_conv2d_forward(*call, w_mode, *tail, _p(ws), ws.numel(), _stream())
-    if rc == 1 and act == ACT_MASK:     # RVSR_ERR_UNSUPPORTED: the fused gradient mask is an option of one kernel, the caller has a plan B
+    if rc == _lib.RVSR_ERR_UNSUPPORTED and act == ACT_MASK:     # the fused gradient mask is an option of one kernel, the caller has a plan B
         return False
     _lib.check(rc, what)
     return True
@@ -1650,7 +1650,7 @@ def _tconv3_run(s, w, bias=None, residual=None, slope=None, transposed=False):
                                             int(transposed), _stream())
         if rc == 0:
             return out, pout
-        if rc != 1:   # RVSR_ERR_UNSUPPORTED: channel counts the kernel does not take -- the composed path below
+        if rc != _lib.RVSR_ERR_UNSUPPORTED:   # channel counts the kernel does not take -- the composed path below
             _lib.check(rc, 'tconv3')
     for i, (dt, a, n, o) in enumerate(_c3_taps(T, 0, T)):
         dst = out[o:o + n]

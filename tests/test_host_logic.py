@@ -28,6 +28,48 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == declared
 
 
+def test_ctypes_signatures_come_from_the_header():
+    """One entry of each kind the header holds, against literal expectations (the table itself is realvsr_amd._lib.parse_header's
+    reading of include/realvsr_hip.h)."""
+    import ctypes as C
+    from realvsr_amd import _lib
+    S = _lib.SIGNATURES
+    p, i, f, d, z = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
+    same = lambda got, want: got[0] is want[0] and len(got[1]) == len(want[1]) and all(a is b for a, b in zip(got[1], want[1]))  # noqa: E731
+    conv_call = [p, i, p, i, p, f, i, i, i, p, p, p, p, i, p, i, i, i, i, i, i, f, i, i, i]
+    expected = {
+        'rvsr_last_error': (C.c_char_p, []),
+        'rvsr_set_gemm_mode': (None, [i]),
+        'rvsr_reduce_workspace_bytes': (z, []),
+        'rvsr_charbonnier_forward': (i, [p, p, z, f, d, p, p, p]),
+        'rvsr_conv2d_forward_plan': (i, conv_call + [C.POINTER(C.c_int)]),                              # host int*
+        'rvsr_conv2d_pack_weights': (z, [p, i, i, i, i, p, z, C.POINTER(C.c_longlong), p]),             # host long long*
+        'rvsr_bn_lrelu_forward': (i, [p] * 9 + [i] * 4 + [f] * 3 + [p, z, p]),                          # argument 5: a DEVICE long long*
+        'rvsr_maxavgpool_forward': (i, [p, p, p, i, i, i, i, p]),                                       # unsigned char*
+        'rvsr_dcn_forward_halo': (i, [p, z, i]),                                                        # const unsigned*, read on the host
+        'rvsr_conv2d_backward_weight': (i, [p, i, p, i, i, i, p, p, f, i, i, i, p, p, i, i, i, i, i, i, i, p, z, p]),   # five lines
+    }
+    for name, want in expected.items():
+        assert same(S[name], want), (name, S[name])
+    assert len(S['rvsr_conv2d_backward_weight'][1]) == 24 and S['rvsr_bn_lrelu_forward'][1][5] is p
+    assert (_lib.RVSR_OK, _lib.RVSR_ERR_UNSUPPORTED, _lib.RVSR_ERR_BAD_ARG, _lib.RVSR_ERR_LAUNCH, _lib.RVSR_ERR_WORKSPACE) == (0, 1, 2, 3, 4)
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """Nothing is skipped: an unmapped type, a marker on a type that has no typed pointer, and a statement that is no prototype all raise,
+    and the message names the entry."""
+    import ctypes as C
+    from realvsr_amd._lib import parse_header
+    sigs, codes = parse_header('#define RVSR_X 7 /* c */\n#define RVSR_HOST\nint rvsr_a(const float* x, /* c */ RVSR_HOST int* n,\n size_t k);')
+    assert codes == {'RVSR_X': 7} and list(sigs) == ['rvsr_a']
+    assert sigs['rvsr_a'][0] is C.c_int and sigs['rvsr_a'][1] == [C.c_void_p, C.POINTER(C.c_int), C.c_size_t]
+    for text in ('int rvsr_ok(int a);\nint rvsr_bad(short x);', 'int rvsr_bad(int a, short* x);', 'short rvsr_bad(void);',
+                 'int rvsr_bad(RVSR_HOST float* x);', 'int rvsr_bad(RVSR_HOST int n);', 'int rvsr_bad(int);', 'int rvsr_bad(int a) int rvsr_b(int a);',
+                 'int rvsr_bad(int a, void (*f)(int));', 'typedef int rvsr_bad;', 'int rvsr_bad(int a);\nfloat rvsr_bad(int a);'):
+        with pytest.raises(ValueError, match='rvsr_bad'):
+            parse_header(text)
+
+
 def test_operators_refuse_cpu_tensors():
     from realvsr_amd.archs.dcn import modulated_deform_conv, ModulatedDeformConvPack
     from realvsr_amd.archs.EDVR_arch import EDVR
