@@ -293,6 +293,28 @@ int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, c
                              const float* residual, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
                              int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout,
                              RVSR_HOST int* plan);
+/* The same call with a periodic addend in front of the activation (the PCD stage's conv(cat(x, ref.repeat(N))) = conv_a(x) + conv_b(ref),
+ * realvsr_amd.functional.conv_cat_bcast):
+ *     out1[b] = act((conv(x)[b] + bias) + addend[b % addend_period])
+ *   addend: (addend_period, Co1, Hout, Wout), in the place of `residual`; frame-major x [N * B] with addend_period = B adds partial b to
+ *   the N frames of window b.  conv + bias is rounded to f32 before the addend joins: the result is bit for bit what rvsr_conv2d_forward
+ *   (act 0) followed by rvsr_bcast_add_act stores, without that pass's read and write of the output.
+ *   addend_period 0: rvsr_conv2d_forward, argument for argument (`addend` is then its residual, added after the activation) -- one body
+ *   serves both entries.  addend_period > 0 is an epilogue of the 8 x 64-tile conv_fwd5 kernel only: 3x3, stride 1, more than 32 output
+ *   channels, a 16-byte-aligned plain input view and output with W % 4 == 0, one output, no pixel shuffle, not GEMM mode 1, not act 3.
+ *   Every other call is refused by the plan with RVSR_ERR_UNSUPPORTED and an empty message, nothing is launched, and the caller runs the
+ *   conv and rvsr_bcast_add_act instead.  rvsr_conv2d_forward_addend_plan is to it what rvsr_conv2d_forward_plan is to
+ *   rvsr_conv2d_forward. */
+int rvsr_conv2d_forward_addend(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
+                               int in_mode, int Hs, int Ws, const float* weight, const float* bias,
+                               const float* addend, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
+                               int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout,
+                               int addend_period, void* workspace, size_t workspace_bytes, void* stream);
+int rvsr_conv2d_forward_addend_plan(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
+                                    int in_mode, int Hs, int Ws, const float* weight, const float* bias,
+                                    const float* addend, float* out1, int Co1, float* out2, int Co2, int B, int ksize,
+                                    int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout, int Wout,
+                                    int addend_period, RVSR_HOST int* plan);
 
 /* 2b. Packed weight images, once per optimizer step.  The matrix-core kernels stage weights as bf16 hi/lo images
  *   ([m-block][chunk][hi|lo][tap][octet][row][8]); rvsr_conv2d_forward builds that image in its workspace on every call.

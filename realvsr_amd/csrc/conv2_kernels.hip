@@ -155,6 +155,9 @@ template <int MT, int MODE>
 __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const ConvFwdParams& p, const float* bias_s, int b,
                                                     int o0, int row, int x0, int lo, int hi) {
     if (row >= p.Hout) return;   // wave-uniform
+    // MODE 5 (rvsr_conv2d_forward_addend): out = act((acc + bias) + res[b % res_period]) -- the MODE 1 load from a view that is periodic
+    // over the batch, added BEFORE the activation, which therefore runs on the permuted values next to the add.  acc + bias is rounded
+    // to f32 before the addend joins, so the result is, bit for bit, what a plain conv followed by rvsr_bcast_add_act stores.
     const float neg = (p.act == 0 || MODE == 4) ? 1.f : (p.act == 1 ? 0.f : p.slope);
     // After transpose + half swap lane 4 G + j holds channel j, pixel quad G = 8 hi + (lo >> 2) of the row.  The store path wants
     // CONSECUTIVE lanes on consecutive addresses (store_micro.hip: 4 x 256 B per instruction = 26 B/clk with lanes 16 c .. 16 c + 15
@@ -167,7 +170,9 @@ __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const 
     // raw buffer addressing as in conv2_epilogue_v4: a 32-bit lane offset computed once per row + the channel group's offset, added on the vector side
     const unsigned HW = (unsigned)(p.Hout * p.Wout), HW4 = 4u * HW;
     const __amdgpu_buffer_rsrc_t out_rs = buf_view_2g(p.out1 + (size_t)b * p.Co * HW);
-    const __amdgpu_buffer_rsrc_t res_rs = buf_view_2g(MODE == 1 || MODE == 4 ? p.res + (size_t)b * p.Co * HW : p.out1);
+    const __amdgpu_buffer_rsrc_t res_rs = buf_view_2g(MODE == 5   ? p.res + (size_t)(b % p.res_period) * p.Co * HW
+                                                      : MODE == 1 || MODE == 4 ? p.res + (size_t)b * p.Co * HW
+                                                                               : p.out1);
     const unsigned lane_off = 4u * ((unsigned)jn * HW + (unsigned)row * p.Wout + col4);
     const int j = lo & 3;
 #pragma unroll
@@ -180,7 +185,7 @@ __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const 
             for (int s = 0; s < 2; ++s) {
                 const int ob = o0 + m * 32 + 8 * rg + 4 * s;   // (uniform) first of the instruction's 4 channels
                 off[s] = col_ok && ob + jn < p.Co ? lane_off : 0x80000000u;
-                if (MODE == 1 || MODE == 4) {
+                if (MODE == 1 || MODE == 4 || MODE == 5) {
                     typedef float f32x4v __attribute__((ext_vector_type(4)));
                     const f32x4v q = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(res_rs, (int)(off[s] + (unsigned)ob * HW4), 0, 0));
                     resv[s] = make_float4(q.x, q.y, q.z, q.w);
@@ -195,7 +200,7 @@ __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float v = r[n][e] + bb;
-                    r[n][e] = v > 0.f ? v : v * neg;
+                    r[n][e] = MODE == 5 ? v : (v > 0.f ? v : v * neg);
                 }
             }
 #pragma unroll
@@ -208,7 +213,11 @@ __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const 
 #pragma unroll
             for (int s = 0; s < 2; ++s) {   // set s: lanes 16 c .. 16 c + 15 = channel 8 rg + 4 s + c, the 64 pixels of the row
                 float4 v = make_float4(r[s][0], r[s][1], r[s][2], r[s][3]);
-                if (MODE == 1) { v.x += resv[s].x; v.y += resv[s].y; v.z += resv[s].z; v.w += resv[s].w; }
+                if (MODE == 1 || MODE == 5) { v.x += resv[s].x; v.y += resv[s].y; v.z += resv[s].z; v.w += resv[s].w; }
+                if (MODE == 5) {
+                    v.x = v.x > 0.f ? v.x : v.x * neg; v.y = v.y > 0.f ? v.y : v.y * neg;
+                    v.z = v.z > 0.f ? v.z : v.z * neg; v.w = v.w > 0.f ? v.w : v.w * neg;
+                }
                 if (MODE == 4) {   // gradient mask: the derivative of the activation whose output `res` is (p.act == 3, neg == 1 above)
                     v.x *= resv[s].x > 0.f ? 1.f : p.slope; v.y *= resv[s].y > 0.f ? 1.f : p.slope;
                     v.z *= resv[s].z > 0.f ? 1.f : p.slope; v.w *= resv[s].w > 0.f ? 1.f : p.slope;
@@ -949,6 +958,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
             const float* bias_s = bias_base + (k & 3) * MP;
             if (WIDE) {   // (conv_fwd_plan: 16-byte stores, no pixel shuffle, one output tensor)
                 if (p.act == 3) conv2_epilogue_wide<MT, 4>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
+                else if (p.res_period > 0) conv2_epilogue_wide<MT, 5>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else if (p.res != nullptr) conv2_epilogue_wide<MT, 1>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else conv2_epilogue_wide<MT, 0>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
             } else if (p.ps)

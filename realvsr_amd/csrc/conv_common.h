@@ -22,6 +22,9 @@ struct ConvFwdParams {
     float slope;
     int ps;
     int ntx;
+    int res_period;     // > 0: `res` is an addend (res_period, Co, Hout, Wout) read at batch element b % res_period and added BEFORE the
+                        // activation (rvsr_conv2d_forward_addend); 0: the residual of rvsr_conv2d_forward, added after it.  (Last, so
+                        // that every older field keeps its offset in the kernel argument block.)
 };
 
 

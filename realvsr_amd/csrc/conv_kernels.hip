@@ -305,16 +305,18 @@ static int make_view(TView& v, const float* p, const float* act, float slope, in
 static int conv_fwd_params(ConvFwdParams& p, const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope,
                            int in_mode, int Hs, int Ws, const float* weight, const float* bias, const float* residual, float* out1,
                            int Co1, float* out2, int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
-                           int pixel_shuffle, int Hout, int Wout) {
+                           int pixel_shuffle, int Hout, int Wout, int addend_period) {
     if (!x1 || !weight || !out1 || B <= 0 || C1 <= 0 || Co1 <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d: null/empty argument");
+    if (addend_period < 0 || (addend_period > 0 && !residual)) FAIL(RVSR_ERR_BAD_ARG, "conv2d: addend period %d without an addend", addend_period);
     if ((x2 == nullptr) != (C2 == 0) || (out2 == nullptr) != (Co2 == 0))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: second input/output pointer and channel count disagree");
     if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 or 5 supported)", ksize);
     if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: stride %d", stride);
     if (in_mode != 0 && (x2 != nullptr || stride != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: view mode with concat/stride");
     if (xact && x2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: act' fusion with concat input");
-    if ((residual || pixel_shuffle) && out2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual/pixel-shuffle with split output");
-    if (residual && pixel_shuffle) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual with pixel-shuffle");
+    // (an addend with a split or pixel-shuffled output is the plan's to refuse, silently: the caller has a plan B)
+    if ((residual || pixel_shuffle) && out2 && !addend_period) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual/pixel-shuffle with split output");
+    if (residual && pixel_shuffle && !addend_period) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: residual with pixel-shuffle");
     if (make_view(p.in.a, x1, xact, xact_slope, C1, Hs, Ws, in_mode, Hout, Wout))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: bad input view (mode %d, C %d, %dx%d)", in_mode, C1, Hs, Ws);
     make_view(p.in.b, x2, nullptr, 0.f, C2, Hs, Ws, 0, 0, 0);
@@ -327,6 +329,7 @@ static int conv_fwd_params(ConvFwdParams& p, const float* x1, int C1, const floa
     p.vec4 = 0;
     p.bias = bias;
     p.res = residual;
+    p.res_period = addend_period;
     p.out1 = out1;
     p.out2 = out2;
     p.Co1 = Co1;
@@ -350,16 +353,15 @@ static int conv_fwd_refuse(const ConvFwdPlan& q) {
     return q.rc;
 }
 
-// Fused conv block.  See include/realvsr_hip.h for the contract: validate, plan (conv_plan.h), refuse or launch.
-extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const float* xact,
-                                   float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
-                                   const float* bias, const float* residual, float* out1, int Co1, float* out2,
-                                   int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
-                                   int pixel_shuffle, int Hout, int Wout, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
+// Fused conv block.  See include/realvsr_hip.h for the contract: validate, plan (conv_plan.h), refuse or launch.  One body behind
+// rvsr_conv2d_forward (addend_period 0) and rvsr_conv2d_forward_addend.
+static int conv2d_forward_call(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope, int in_mode, int Hs,
+                               int Ws, const float* weight, const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                               int Co2, int B, int ksize, int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout,
+                               int Wout, int addend_period, void* workspace, size_t workspace_bytes, void* stream) {
     ConvFwdParams p;
     const int rc = conv_fwd_params(p, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B,
-                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout);
+                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, addend_period);
     if (rc) return rc;
     const ConvFwdPlan q = conv_fwd_plan(p, ksize, stride, rvsr_gemm_mode_now());
     if (q.rc) return conv_fwd_refuse(q);
@@ -371,19 +373,53 @@ extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int
     }
 }
 // The plan of that call, without a GPU: same arguments, same return code (and rvsr_last_error), nothing launched.
-extern "C" int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, const float* xact,
-                                        float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
-                                        const float* bias, const float* residual, float* out1, int Co1, float* out2,
-                                        int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
-                                        int pixel_shuffle, int Hout, int Wout, int* plan) {
+static int conv2d_forward_plan_of(const float* x1, int C1, const float* x2, int C2, const float* xact, float xact_slope, int in_mode, int Hs,
+                                  int Ws, const float* weight, const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                                  int Co2, int B, int ksize, int stride, int w_mode, int act, float slope, int pixel_shuffle, int Hout,
+                                  int Wout, int addend_period, int* plan) {
     ConvFwdParams p;
     const int rc = conv_fwd_params(p, x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B,
-                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout);
+                                   ksize, stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, addend_period);
     if (rc) return rc;
     const ConvFwdPlan q = conv_fwd_plan(p, ksize, stride, rvsr_gemm_mode_now());
     const int row[14] = {q.family, q.mt, q.vec, q.wide, q.nt, q.act_in, q.cc, q.vec4, q.th, q.tw, (int)q.gx, (int)q.gy, (int)q.gz, (int)q.lds};
     for (int i = 0; plan && i < 14; ++i) plan[i] = row[i];
     return q.rc ? conv_fwd_refuse(q) : RVSR_OK;
+}
+extern "C" int rvsr_conv2d_forward(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                   float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                   const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                                   int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                   int pixel_shuffle, int Hout, int Wout, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return conv2d_forward_call(x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, ksize,
+                               stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, 0, workspace, workspace_bytes, stream);
+}
+extern "C" int rvsr_conv2d_forward_plan(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                        float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                        const float* bias, const float* residual, float* out1, int Co1, float* out2,
+                                        int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                        int pixel_shuffle, int Hout, int Wout, int* plan) {
+    return conv2d_forward_plan_of(x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, residual, out1, Co1, out2, Co2, B, ksize,
+                                  stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, 0, plan);
+}
+// out = act((conv + bias) + addend[b % addend_period]): `addend` (addend_period, Co1, Hout, Wout) takes the place of the residual
+extern "C" int rvsr_conv2d_forward_addend(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                          float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                          const float* bias, const float* addend, float* out1, int Co1, float* out2,
+                                          int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                          int pixel_shuffle, int Hout, int Wout, int addend_period, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return conv2d_forward_call(x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, addend, out1, Co1, out2, Co2, B, ksize,
+                               stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, addend_period, workspace, workspace_bytes, stream);
+}
+extern "C" int rvsr_conv2d_forward_addend_plan(const float* x1, int C1, const float* x2, int C2, const float* xact,
+                                               float xact_slope, int in_mode, int Hs, int Ws, const float* weight,
+                                               const float* bias, const float* addend, float* out1, int Co1, float* out2,
+                                               int Co2, int B, int ksize, int stride, int w_mode, int act, float slope,
+                                               int pixel_shuffle, int Hout, int Wout, int addend_period, int* plan) {
+    return conv2d_forward_plan_of(x1, C1, x2, C2, xact, xact_slope, in_mode, Hs, Ws, weight, bias, addend, out1, Co1, out2, Co2, B, ksize,
+                                  stride, w_mode, act, slope, pixel_shuffle, Hout, Wout, addend_period, plan);
 }
 
 int rvsr_g_gemm_mode = 0;                  // process-wide default

@@ -78,6 +78,9 @@ static inline ConvFwdPlan conv_fwd_plan(const ConvFwdParams& p, int ksize, int s
     const int Ctot = va.C + vb.C, T = ksize * ksize;
     // act 3, out = (conv + bias) * (residual > 0 ? 1 : slope): an epilogue of the 8 x 64-tile conv_fwd5 kernel only
     if (p.act == 3 && (!p.res || ksize != 3 || stride != 1 || p.ps || p.out2 || gemm_mode == 1)) return conv_fwd_refusal(nullptr);
+    // a periodic addend in front of the activation, out = act((conv + bias) + res[b % res_period]): an epilogue of that kernel only, too
+    // (refused like the mask: the caller adds the broadcast partial in a pass of its own, rvsr_bcast_add_act)
+    if (p.res_period > 0 && (p.act == 3 || ksize != 3 || stride != 1 || p.ps || p.out2 || gemm_mode == 1)) return conv_fwd_refusal(nullptr);
     ConvFwdPlan q = {};
     q.act_in = va.act != nullptr;
     q.nt = 3;
@@ -88,7 +91,7 @@ static inline ConvFwdPlan conv_fwd_plan(const ConvFwdParams& p, int ksize, int s
     const int ntx = (p.Wout + 31) / 32, nty8 = (p.Hout + 7) / 8;
 
     // ---- family
-    bool split = p.act == 3;   // the bf16-split kernels, conv_fwd5 / conv_fwd2
+    bool split = p.act == 3 || p.res_period > 0;   // the bf16-split kernels, conv_fwd5 / conv_fwd2
     const bool thin = !split && conv_fwd_thin_ok(p, ksize, stride);
     if (!split && !thin) {
         // GEMM mode 1 is exact f32 everywhere; 5x5 through the zero-insert view of a stride-2 data gradient (in_mode 1) is staged by
@@ -157,7 +160,7 @@ static inline ConvFwdPlan conv_fwd_plan(const ConvFwdParams& p, int ksize, int s
     // pixels than 16 x 32
     const long px_n = (long)((p.Hout + 15) / 16 * 16) * ((p.Wout + 31) / 32 * 32), px_w = (long)((p.Hout + 7) / 8 * 8) * ((p.Wout + 63) / 64 * 64);
     q.wide = q.mt == 2 && q.vec == 1 && q.vec4 && px_w <= px_n;
-    if (p.act == 3 && !q.wide) return conv_fwd_refusal(nullptr);   // (mask epilogue: 8 x 64 tile only)
+    if ((p.act == 3 || p.res_period > 0) && !q.wide) return conv_fwd_refusal(nullptr);   // (mask and addend epilogues: 8 x 64 tile only)
     // reduced-term products (GEMM modes 2 / 3): the 64-row m-block kernels on the vector-staged views; everything else keeps three terms
     if (p.fmt) q.nt = 4;
     else if (q.mt == 2 && q.vec != 0) q.nt = gemm_mode == 2 ? 2 : (gemm_mode == 3 ? 1 : 3);

@@ -7,7 +7,8 @@
 //     conv_gauss / upsample as stand-alone operators                          utils/util.py:503-554
 //   * YCbCr -> BGR uint8 for the inference path, the MFMA rate aid of bench.py, and the library's error string (rvsr_last_error)
 // The scalar losses live in train_kernels.hip.
-// All kernels: one thread per output element, lanes along W (coalesced), grid-stride loops.
+// All kernels: one thread per output element (the *_v4 kernels: 4 adjacent elements of a row, 16-byte accesses), lanes along W
+// (coalesced), grid-stride loops.
 // Backward kernels are gathers that re-evaluate the forward index map over a conservative
 // candidate window (no atomics -> deterministic).
 #define RVSR_DEFINE_REDUCE
@@ -132,6 +133,48 @@ __global__ void upsample2_bwd_kernel(const float* __restrict__ gout, float* __re
     }
 }
 
+// Backward with W % 4 == 0 and 16-byte aligned pointers: one thread per FOUR adjacent input pixels of a row, the four output rows as
+// two 16-byte loads plus the two neighbours each, one 16-byte store, two 32-bit divisions per thread instead of two per pixel:
+// 0.255 against 0.309 ms on 40 x 64 x 180 x 320 -> 90 x 160.  (The forward stays on the float2 kernel.  Two 16-byte forms of it were
+// built and measured against its 0.216 ms on 40 x 64 x 90 x 160: four pixels per thread, 2 x 8 outputs as four 16-byte stores, 0.224 ms
+// -- a lane then owns 32 bytes of a row and a store instruction fills every other 16 bytes of its span; two pixels per thread, two
+// contiguous 16-byte stores, 0.214 ms there but 6 % slower over the step's 48 launches.  profiles/r12_notes.md section 5.)
+// ARITHMETIC: the float2 kernel above leaves it to the compiler which product of a sum a * b + c * d is fused into the add and which
+// is rounded first, and what it chose (read from its gfx950 code) is not uniform over the terms.  The results of that kernel are
+// the library's results, so the v4 kernel spells that choice out -- fmaf where the float2 code fuses, a rounded product where it
+// does not, contraction off -- and gives the same bits on any input (tests/test_gpu_glue_vector.py compares the two on random values).
+__global__ void upsample2_bwd_v4_kernel(const float* __restrict__ gout, float* __restrict__ gin, unsigned planes, int H, int W, float scale) {
+#pragma clang fp contract(off)
+    const unsigned W4 = (unsigned)W >> 2, n = planes * (unsigned)H * W4;
+    const int Wo = 2 * W;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const unsigned row = i / W4, pl = row / (unsigned)H;
+        const int x0 = (int)((i - row * W4) << 2), y = (int)(row - pl * (unsigned)H);
+        const float* g = gout + (size_t)pl * 4 * H * W;
+        const float wy[4] = {y > 0 ? 0.25f : 0.f, y > 0 ? 0.75f : 1.f, y < H - 1 ? 0.75f : 1.f, y < H - 1 ? 0.25f : 0.f};
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            int oy = 2 * y - 1 + a;
+            oy = oy < 0 ? 0 : (oy > 2 * H - 1 ? 2 * H - 1 : oy);    // clamped rows carry weight 0
+            const float* q = g + (size_t)oy * Wo + 2 * x0;
+            const float4 m0 = reinterpret_cast<const float4*>(q)[0], m1 = reinterpret_cast<const float4*>(q)[1];
+            // cols 2 x0 - 1 .. 2 x0 + 8; the two outer ones clamp onto the row's ends, where their weight is 0
+            const float c[10] = {q[x0 > 0 ? -1 : 0], m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, q[x0 + 4 < W ? 8 : 7]};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k;
+                const float wx0 = x > 0 ? 0.25f : 0.f, wx1 = x > 0 ? 0.75f : 1.f, wx2 = x < W - 1 ? 0.75f : 1.f, wx3 = x < W - 1 ? 0.25f : 0.f;
+                // the float2 kernel's row sum: rows 2y - 1 .. 2y + 1 round wx2 * c before adding it, row 2y + 2 fuses it
+                const float s01 = fmaf(wx1, c[2 * k + 1], wx0 * c[2 * k]);
+                const float s012 = a < 3 ? wx2 * c[2 * k + 2] + s01 : fmaf(wx2, c[2 * k + 2], s01);
+                acc[k] = fmaf(wy[a], fmaf(wx3, c[2 * k + 3], s012), acc[k]);
+            }
+        }
+        *reinterpret_cast<float4*>(gin + (size_t)row * W + x0) = make_float4(acc[0] * scale, acc[1] * scale, acc[2] * scale, acc[3] * scale);
+    }
+}
+
 // ---------------------------------------------------------------- max+avg pool 3/2/1 -> cat
 __global__ void pool_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, unsigned char* __restrict__ arg,
                                 int B, int C, int H, int W, int Ho, int Wo) {
@@ -189,6 +232,96 @@ __global__ void pool_bwd_kernel(const float* __restrict__ gout, const unsigned c
             }
         }
         gin[i] = acc;
+    }
+}
+
+// W % 8 == 0 (forward) / W % 4 == 0 (backward) and 16-byte aligned pointers, fewer than 2^31 elements: one thread per FOUR adjacent
+// outputs (forward) or inputs (backward) of a row, 32-bit indices.  Forward: the three source rows as two 16-byte loads plus the left
+// neighbour, both halves and the argmax written as 16- / 4-byte stores.  Taps are visited in the scan order of the kernels above
+// (first maximum wins, a NaN wins, the sum adds in that order), so the results are theirs bit for bit.
+__global__ void pool_fwd_v4_kernel(const float* __restrict__ in, float* __restrict__ out, unsigned char* __restrict__ arg,
+                                   int B, int C, int H, int W, int Ho, int Wo) {
+    const unsigned Wq = (unsigned)Wo >> 2, n = (unsigned)B * C * Ho * Wq;
+    const unsigned hw = (unsigned)Ho * Wo;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const unsigned row = i / Wq, pl = row / (unsigned)Ho, b = pl / (unsigned)C;
+        const int ox0 = (int)((i - row * Wq) << 2), oy = (int)(row - pl * (unsigned)Ho), c = (int)(pl - b * (unsigned)C);
+        const float* p = in + (size_t)pl * H * W;
+        float v[3][9];      // rows 2 oy - 1 .. 2 oy + 1, cols 2 ox0 - 1 .. 2 ox0 + 7 (all inside the row but col -1)
+        bool rowok[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int y = 2 * oy - 1 + r;
+            rowok[r] = y >= 0 && y < H;
+            const float* q = p + (size_t)(rowok[r] ? y : 2 * oy) * W + 2 * ox0;
+            const float4 m0 = reinterpret_cast<const float4*>(q)[0], m1 = reinterpret_cast<const float4*>(q)[1];
+            v[r][0] = q[ox0 > 0 ? -1 : 0];
+            v[r][1] = m0.x, v[r][2] = m0.y, v[r][3] = m0.z, v[r][4] = m0.w;
+            v[r][5] = m1.x, v[r][6] = m1.y, v[r][7] = m1.z, v[r][8] = m1.w;
+        }
+        float mxs[4], avs[4];
+        unsigned ams = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float mx = -INFINITY, sum = 0.f;
+            int am = 0;
+            bool first = true;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                if (!rowok[t / 3] || (t % 3 == 0 && ox0 + k == 0)) continue;
+                const float u = v[t / 3][2 * k + t % 3];
+                sum += u;
+                if (first || u > mx || u != u) {
+                    mx = u;
+                    am = t;
+                    first = false;
+                }
+            }
+            mxs[k] = mx;
+            avs[k] = sum * (1.f / 9.f);  // count_include_pad=True
+            ams |= (unsigned)am << (8 * k);
+        }
+        const unsigned pix = (unsigned)oy * Wo + ox0;
+        *reinterpret_cast<float4*>(out + ((size_t)b * 2 * C + c) * hw + pix) = make_float4(mxs[0], mxs[1], mxs[2], mxs[3]);
+        *reinterpret_cast<float4*>(out + ((size_t)b * 2 * C + C + c) * hw + pix) = make_float4(avs[0], avs[1], avs[2], avs[3]);
+        *reinterpret_cast<unsigned*>(arg + (size_t)pl * hw + pix) = ams;
+    }
+}
+// inputs x0 .. x0 + 3 of row y read the outputs x0 / 2 .. x0 / 2 + 2 of rows y / 2 .. (y + 1) / 2
+__global__ void pool_bwd_v4_kernel(const float* __restrict__ gout, const unsigned char* __restrict__ arg,
+                                   float* __restrict__ gin, int B, int C, int H, int W, int Ho, int Wo) {
+#pragma clang fp contract(off)
+    const unsigned W4 = (unsigned)W >> 2, n = (unsigned)B * C * H * W4;
+    const unsigned hw = (unsigned)Ho * Wo;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const unsigned row = i / W4, pl = row / (unsigned)H, b = pl / (unsigned)C;
+        const int x0 = (int)((i - row * W4) << 2), y = (int)(row - pl * (unsigned)H), c = (int)(pl - b * (unsigned)C);
+        const float* gm = gout + ((size_t)b * 2 * C + c) * hw;
+        const float* ga = gout + ((size_t)b * 2 * C + C + c) * hw;
+        const unsigned char* a = arg + (size_t)pl * hw;
+        const int o0 = x0 >> 1;
+        const bool third = o0 + 2 < Wo;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int oy = y / 2; oy <= (y + 1) / 2; ++oy) {
+            if (oy >= Ho) continue;
+            const unsigned pix = (unsigned)oy * Wo + o0;
+            const float2 m2 = *reinterpret_cast<const float2*>(gm + pix), a2 = *reinterpret_cast<const float2*>(ga + pix);
+            const unsigned short t2 = *reinterpret_cast<const unsigned short*>(a + pix);
+            const float m[3] = {m2.x, m2.y, third ? gm[pix + 2] : 0.f}, av[3] = {a2.x, a2.y, third ? ga[pix + 2] : 0.f};
+            const int ts[3] = {t2 & 255, t2 >> 8, third ? a[pix + 2] : 255};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k;
+#pragma unroll
+                for (int j = k / 2; j <= (k + 1) / 2; ++j) {       // ox = o0 + j, ascending as above
+                    if (j == 2 && !third) continue;
+                    const int t = (y - (2 * oy - 1)) * 3 + (x - (2 * (o0 + j) - 1));
+                    acc[k] = fmaf(av[j], 1.f / 9.f, acc[k]);      // (fused, as pool_bwd_kernel's `acc += ga * (1 / 9)` is)
+                    if (ts[j] == t) acc[k] += m[j];
+                }
+            }
+        }
+        *reinterpret_cast<float4*>(gin + (size_t)row * W + x0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
 }
 
@@ -274,35 +407,92 @@ __global__ void tsa_final_bwd_kernel(const float* __restrict__ g, const float* _
 __device__ __forceinline__ int reflect(int q, int n) { return q < 0 ? -q : (q >= n ? 2 * (n - 1) - q : q); }
 __device__ __forceinline__ float binom(int i) { return i == 0 || i == 4 ? 1.f : (i == 2 ? 6.f : 4.f); }
 
+// idx -> (plane, y, x) of a planes x H x W tensor: two 32-bit divisions while the tensor has fewer than 2^32 elements (every launch
+// of the training step), the 64-bit ones beyond
+__device__ __forceinline__ size_t pyr_split(size_t idx, bool small, int H, int W, int& y, int& x) {
+    if (small) {
+        const unsigned row = (unsigned)idx / (unsigned)W, pl = row / (unsigned)H;
+        x = (int)((unsigned)idx - row * (unsigned)W);
+        y = (int)(row - pl * (unsigned)H);
+        return pl;
+    }
+    x = (int)(idx % W);
+    y = (int)((idx / W) % H);
+    return idx / ((size_t)W * H);
+}
+
+// The four pyramid stencils below have two paths each.  Away from the border no tap reflects: the forward kernels index their taps
+// directly, and the adjoints enumerate the few outputs that read an input -- by parity (1, 6, 1) or (4, 4) for the ::2 select, always
+// (1, 4, 6, 4, 1) for the zero-insert upsample -- instead of testing every tap of a 7- or 9-wide candidate window.  Border rows and
+// columns keep the reflect() / candidate-scan code.  Both paths add the same terms in the same ascending order with the same
+// rowacc / acc grouping, so which path a pixel takes does not show in the bits.
+
+// The 25-tap sum of gauss_down_fwd, v[5 i + j] = in[row i][col j] of the window: taps 0 .. 12 are fused multiply-adds onto the running
+// sum, taps 13 .. 24 are rounded products added to it.  That split is what the compiler made of `acc += w * in[..]` in this kernel
+// since it was written (it packs the later products in pairs) and so defines the operator's bits; written out, it no longer depends
+// on how the taps are addressed.
+__device__ __forceinline__ float gauss_down_sum(const float (&v)[25]) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int t = 0; t < 25; ++t) {
+        const float w = binom(t / 5) * binom(t % 5) * (1.f / 256.f);
+        acc = t < 13 ? fmaf(w, v[t], acc) : acc + w * v[t];
+    }
+    return acc;
+}
+
 // out[y][x] = sum_{i,j} k[i]k[j]/256 * in[reflect(2y+i-2)][reflect(2x+j-2)]     (conv_gauss + ::2)
 __global__ void gauss_down_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int H,
                                       int W, int Hd, int Wd) {
     const size_t n = planes * Hd * Wd;
+    const bool small = n < (1ull << 32);
     LOOP(idx, n) {
-        const int x = (int)(idx % Wd);
-        const int y = (int)((idx / Wd) % Hd);
-        const float* p = in + (idx / ((size_t)Wd * Hd)) * H * W;
-        float acc = 0.f;
+        int x, y;
+        const float* p = in + pyr_split(idx, small, Hd, Wd, y, x) * H * W;
+        float v[25];
+        if (y >= 1 && 2 * y + 2 < H && x >= 1 && 2 * x + 2 < W) {      // interior: rows 2y-2 .. 2y+2, cols 2x-2 .. 2x+2 as they are
+            const float* q = p + (size_t)(2 * y - 2) * W + (2 * x - 2);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int r = reflect(2 * y + i - 2, H);
+            for (int t = 0; t < 25; ++t) v[t] = q[(t / 5) * W + t % 5];
+        } else {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const int s = reflect(2 * x + j - 2, W);
-                acc += (binom(i) * binom(j) * (1.f / 256.f)) * p[(size_t)r * W + s];
+            for (int i = 0; i < 5; ++i) {
+                const int r = reflect(2 * y + i - 2, H);
+#pragma unroll
+                for (int j = 0; j < 5; ++j) v[5 * i + j] = p[(size_t)r * W + reflect(2 * x + j - 2, W)];
             }
         }
-        out[idx] = acc;
+        out[idx] = gauss_down_sum(v);
     }
 }
 
 __global__ void gauss_down_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin, size_t planes, int H,
                                       int W, int Hd, int Wd) {
     const size_t n = planes * H * W;
+    const bool small = n < (1ull << 32);
     LOOP(idx, n) {
-        const int s = (int)(idx % W);
-        const int r = (int)((idx / W) % H);
-        const float* g = gout + (idx / ((size_t)W * H)) * Hd * Wd;
+        int s, r;
+        const float* g = gout + pyr_split(idx, small, H, W, r, s) * Hd * Wd;
+        if (r >= 3 && r <= H - 4 && s >= 3 && s <= W - 4) {
+            // interior: an even row is read by outputs r/2 - 1, r/2, r/2 + 1 through taps 4, 2, 0 (weights 1, 6, 1), an odd row by
+            // r/2, r/2 + 1 through taps 3, 1 (4, 4); no reflected tap lands on rows 3 .. H - 4
+            const int oddr = r & 1, odds = s & 1;
+            const int y0 = r / 2 - 1 + oddr, x0 = s / 2 - 1 + odds;
+            const float wy0 = oddr ? 4.f : 1.f, wy1 = oddr ? 4.f : 6.f, wx0 = odds ? 4.f : 1.f, wx1 = odds ? 4.f : 6.f;
+            float acc = 0.f;
+#pragma unroll
+            for (int ty = 0; ty < 3; ++ty) {      // (every `+= w * g` of this kernel is one fused multiply-add)
+                if (ty == 2 && oddr) continue;
+                const float* q = g + (size_t)(y0 + ty) * Wd + x0;
+                float rowacc = fmaf(wx0, q[0], 0.f);
+                rowacc = fmaf(wx1, q[1], rowacc);
+                if (!odds) rowacc = fmaf(1.f, q[2], rowacc);
+                acc = fmaf(ty == 0 ? wy0 : (ty == 1 ? wy1 : 1.f), rowacc, acc);
+            }
+            gin[idx] = acc * (1.f / 256.f);
+            continue;
+        }
         float wy[7], wx[7];
         const int yb = r / 2 - 3, xb = s / 2 - 3;
 #pragma unroll
@@ -336,11 +526,29 @@ __global__ void lap_updiff_fwd_kernel(const float* __restrict__ cur, const float
                                       float* __restrict__ out, size_t planes, int H, int W) {
     const int Hd = H / 2, Wd = W / 2;
     const size_t n = planes * H * W;
+    const bool small = n < (1ull << 32);
     LOOP(idx, n) {
-        const int x = (int)(idx % W);
-        const int y = (int)((idx / W) % H);
-        const float* d = down + (idx / ((size_t)W * H)) * Hd * Wd;
+        int x, y;
+        const float* d = down + pyr_split(idx, small, H, W, y, x) * Hd * Wd;
         float acc = 0.f;
+        if (y >= 2 && y <= H - 3 && x >= 2 && x <= W - 3) {
+            // interior: the even rows among y-2 .. y+2 are taps 0, 2, 4 (y even) or 1, 3 (y odd), the same along x
+            const int i0 = y & 1, j0 = x & 1;
+            const float* q = d + (size_t)((y + i0 - 2) >> 1) * Wd + ((x + j0 - 2) >> 1);
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii) {
+                if (ii == 2 && i0) continue;
+                const float bi = i0 ? 4.f : (ii == 1 ? 6.f : 1.f);
+#pragma unroll
+                for (int jj = 0; jj < 3; ++jj) {
+                    if (jj == 2 && j0) continue;
+                    const float bj = j0 ? 4.f : (jj == 1 ? 6.f : 1.f);
+                    acc = fmaf(bi * bj * (4.f / 256.f), q[ii * Wd + jj], acc);      // (fused, as every tap of the border path is)
+                }
+            }
+            out[idx] = cur[idx] - acc;
+            continue;
+        }
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             const int r = reflect(y + i - 2, H);
@@ -361,10 +569,24 @@ __global__ void lap_updiff_bwd_kernel(const float* __restrict__ gout, float* __r
                                       int W) {
     const int Hd = H / 2, Wd = W / 2;
     const size_t n = planes * Hd * Wd;
+    const bool small = n < (1ull << 32);
     LOOP(idx, n) {
-        const int b = (int)(idx % Wd);
-        const int a = (int)((idx / Wd) % Hd);
-        const float* g = gout + (idx / ((size_t)Wd * Hd)) * H * W;
+        int a, b;
+        const float* g = gout + pyr_split(idx, small, Hd, Wd, a, b) * H * W;
+        if (a >= 2 && a <= Hd - 2 && b >= 2 && b <= Wd - 2) {
+            // interior: rows 2a-2 .. 2a+2 reach row 2a through taps 4 .. 0 (weights 1, 4, 6, 4, 1); no reflected tap lands on it
+            const float* q = g + (size_t)(2 * a - 2) * W + (2 * b - 2);
+            float acc = 0.f;
+#pragma unroll
+            for (int ty = 0; ty < 5; ++ty) {
+                float rowacc = 0.f;      // (every `+= w * g` of this kernel is one fused multiply-add)
+#pragma unroll
+                for (int tx = 0; tx < 5; ++tx) rowacc = fmaf(binom(tx), q[ty * W + tx], rowacc);
+                acc = fmaf(binom(ty), rowacc, acc);
+            }
+            gdown[idx] = -acc * (4.f / 256.f);
+            continue;
+        }
         float wy[9], wx[9];
         const int yb = 2 * a - 4, xb = 2 * b - 4;
 #pragma unroll
@@ -476,6 +698,10 @@ extern "C" int rvsr_upsample_bilinear_backward(const float* gout, float* gin, si
                                                float scale, void* stream) {
     if (!gout || !gin || (factor != 2 && factor != 4)) FAIL(RVSR_ERR_BAD_ARG, "upsample backward: bad argument");
     const size_t n = planes * H * W;
+    if (factor == 2 && n * 4 < (1ull << 32) && W % 4 == 0 && ((((uintptr_t)gout) | ((uintptr_t)gin)) & 15) == 0) {
+        hipLaunchKernelGGL(upsample2_bwd_v4_kernel, GRID_FOR(n / 4), dim3(256), 0, (hipStream_t)stream, gout, gin, (unsigned)planes, H, W, scale);
+        RETURN_LAUNCH("upsample2_bwd_v4");
+    }
     if (factor == 2 && n * 4 < (1ull << 32) && (((uintptr_t)gout) & 7) == 0) {
         hipLaunchKernelGGL(upsample2_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, gin, (unsigned)planes, H, W, scale);
         RETURN_LAUNCH("upsample2_bwd");
@@ -488,6 +714,10 @@ extern "C" int rvsr_maxavgpool_forward(const float* in, float* out, unsigned cha
     if (!in || !out || !argmax) FAIL(RVSR_ERR_BAD_ARG, "pool: null argument");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t n = (size_t)B * C * Ho * Wo;
+    if (W % 8 == 0 && (size_t)B * C * H * W < (1ull << 31) && ((((uintptr_t)in) | ((uintptr_t)out) | ((uintptr_t)argmax)) & 15) == 0) {
+        hipLaunchKernelGGL(pool_fwd_v4_kernel, GRID_FOR(n / 4), dim3(256), 0, (hipStream_t)stream, in, out, argmax, B, C, H, W, Ho, Wo);
+        RETURN_LAUNCH("pool_fwd_v4");
+    }
     hipLaunchKernelGGL(pool_fwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, in, out, argmax, B, C, H, W, Ho, Wo);
     RETURN_LAUNCH("pool_fwd");
 }
@@ -496,6 +726,10 @@ extern "C" int rvsr_maxavgpool_backward(const float* gout, const unsigned char* 
     if (!gout || !gin || !argmax) FAIL(RVSR_ERR_BAD_ARG, "pool backward: null argument");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t n = (size_t)B * C * H * W;
+    if (W % 4 == 0 && n < (1ull << 31) && ((((uintptr_t)gout) | ((uintptr_t)gin) | ((uintptr_t)argmax)) & 15) == 0) {
+        hipLaunchKernelGGL(pool_bwd_v4_kernel, GRID_FOR(n / 4), dim3(256), 0, (hipStream_t)stream, gout, argmax, gin, B, C, H, W, Ho, Wo);
+        RETURN_LAUNCH("pool_bwd_v4");
+    }
     hipLaunchKernelGGL(pool_bwd_kernel, GRID_FOR(n), dim3(256), 0, (hipStream_t)stream, gout, argmax, gin, B, C, H, W, Ho, Wo);
     RETURN_LAUNCH("pool_bwd");
 }

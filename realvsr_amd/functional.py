@@ -88,6 +88,7 @@ class GradSink:
 
 _ADOPT_FLAT_GRADS = True   # parameter gradients are written in place of the flat buffer (optim.FlatBuffers)
 _FUSE_GRAD_MASK = True     # ResBlock backward: relu' of the hidden activation in the epilogue of conv2's data gradient
+_FUSE_BCAST_ADDEND = True  # conv_cat_bcast forward: conv_b's partial as a periodic addend of conv_a's epilogue (rvsr_conv2d_forward_addend)
 
 
 def _pgrad(p, zero=False):
@@ -124,12 +125,14 @@ def invalidate_weight_cache():
 
 
 def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode=0, bias=None, residual=None, out2=None, stride=1,
-          transposed=False, act=ACT_NONE, slope=0.0, pixel_shuffle=False):
+          transposed=False, act=ACT_NONE, slope=0.0, pixel_shuffle=False, addend_period=0):
     """rvsr_conv2d_forward (include/realvsr_hip.h section 2) on contiguous [..., C, H, W] tensors, which carry the geometry (leading
     dimensions fold into the batch): out1 [, out2] = act(conv(cat(x1, x2)) + bias) [+ residual].  transposed: `weight` is
     (C_in, Co, k, k), used transposed and flipped (a data gradient).  in_mode 2: x1 is stored pixel-shuffled, (B, C1/4, Hs, Ws);
     pixel_shuffle: out1 is (B, Co/4, 2*Hout, 2*Wout).  The weight image comes from the per-step cache when `weight` lives in FlatBuffers
-    (or is a cached slice of such a parameter), else it is packed per call into the shared scratch."""
+    (or is a cached slice of such a parameter), else it is packed per call into the shared scratch.
+    addend_period P > 0 (rvsr_conv2d_forward_addend): `residual` is a (P, Co, Hout, Wout) addend, out1[b] = act(conv + bias +
+    residual[b % P]); returns False, having launched nothing, where the library has no such epilogue -- the caller has a plan B."""
     C1, Hs, Ws = x1.shape[-3:]
     if in_mode == 2:
         C1 *= 4
@@ -155,8 +158,11 @@ def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode
         ws, w_mode = buf, w_mode | 2
     else:
         ws = _workspace(nbytes, torch.device('cuda', torch.cuda.current_device()))
-    rc = L.rvsr_conv2d_forward(*call, w_mode, *tail, _p(ws), ws.numel(), _stream())
-    if rc == _lib.RVSR_ERR_UNSUPPORTED and act == ACT_MASK:     # the fused gradient mask is an option of one kernel, the caller has a plan B
+    if addend_period:
+        rc = L.rvsr_conv2d_forward_addend(*call, w_mode, *tail, addend_period, _p(ws), ws.numel(), _stream())
+    else:
+        rc = L.rvsr_conv2d_forward(*call, w_mode, *tail, _p(ws), ws.numel(), _stream())
+    if rc == _lib.RVSR_ERR_UNSUPPORTED and (act == ACT_MASK or addend_period):   # an option of one kernel, the caller has a plan B
         return False
     _lib.check(rc, what)
     return True
@@ -354,9 +360,12 @@ class _ConvCatBcast(Function):
         w_a, w_b = packed_weights.split(weight, C1)   # persistent per-step copies when the weight lives in FlatBuffers
         out = x.new_empty(NB, Co, H, W)
         part = x.new_empty(B, Co, H, W)
-        _conv(x, w_a, out, bias=bias, what='conv_cat_bcast conv_a')
         _conv(ref, w_b, part, what='conv_cat_bcast conv_b')
-        _lib.check(_lib.lib().rvsr_bcast_add_act(_p(out), _p(part), part.numel(), N, act, slope, _stream()), 'bcast_add_act')
+        # the partial as an addend of conv_a's epilogue where that kernel has one (8 x 64 tile), else a pass of its own over `out`
+        if not (_FUSE_BCAST_ADDEND and _conv(x, w_a, out, bias=bias, residual=part, addend_period=B, act=act, slope=slope,
+                                             what='conv_cat_bcast conv_a')):
+            _conv(x, w_a, out, bias=bias, what='conv_cat_bcast conv_a')
+            _lib.check(_lib.lib().rvsr_bcast_add_act(_p(out), _p(part), part.numel(), N, act, slope, _stream()), 'bcast_add_act')
         ctx.cfg = (N, act, slope, bias is not None)
         ctx.w_ab = (w_a, w_b)   # (python references: the cached slices carry the attribute the weight-image cache keys on)
         # the cached slices are PERSISTENT tensors that repack() / split() overwrite in place, behind save_for_backward's version
