@@ -269,6 +269,8 @@ int rvsr_deform_conv_generic_backward(int dtype, const void* input, const void* 
  *   pixel_shuffle 1: out1 is (B,Co/4,2*Hout,2*Wout), written through PixelShuffle(2).
  *   stride 2 only with ksize 3 or 5 and in_mode 0.
  *   ksize 5 (pad 2; the patch discriminator, discriminator_arch.py:46-92): stride-2 data gradients through in_mode 1 as for 3x3.
+ *   ksize 7 (pad 3; SpyNet's blocks, TOF_arch.py:18-27): stride 1 only, on the exact-f32 kernel in every GEMM mode (no packed image:
+ *   the workspace query is 0); w_mode | 4 is refused as for every other ineligible call.
  *   workspace: rvsr_conv2d_forward_workspace_bytes(C1, C2, Co1+Co2, ksize) bytes (holds the weights re-packed as bf16 hi/lo for the
  *   matrix cores; needed by the matrix-core kernels only).
  *   Which kernel a call runs -- the vector-ALU kernel for <= 4 output channels, conv_fwd5 (3x3 stride 1) or conv_fwd2 (3x3 stride 2,
@@ -339,8 +341,8 @@ int rvsr_pack_weights_batched(const void* descs, int n, void* stream);
  *         g_mode 2: stored (B,Co/4,Gs_h,Gs_w) pixel-shuffled (2*Hout, 2*Wout).
  *   gact/gact_slope: fused activation derivative (stored like gout), or NULL.
  *   accumulate 0: overwrite, 1: += .  Deterministic (fixed-order reduction of partials).
- *   Ten kernel families (vector ALU for <= 4 output channels; conv_wgrad2 / conv_wgrad5 / conv_wgrad1x1s / conv_wgrad1x1 /
- *   conv_wgrad_s2 on the bf16 matrix cores; an exact-f32 kernel per geometry, which also serves GEMM mode 1): conv_wgrad_plan
+ *   Eleven kernel families (vector ALU for <= 4 output channels; conv_wgrad2 / conv_wgrad5 / conv_wgrad1x1s / conv_wgrad1x1 /
+ *   conv_wgrad_s2 on the bf16 matrix cores; an exact-f32 kernel per geometry, which also serves GEMM mode 1 and is the only one 7x7 has): conv_wgrad_plan
  *   (csrc/conv_plan.h) picks one and its slicing into partial sums; the workspace query sizes for the largest slicing any family of
  *   the geometry can ask for.  A 1x1 weight gradient runs the LDS-staged conv_wgrad1x1s when gout is plain (g_mode 0), Hout * Wout is
  *   a multiple of 4, all pointers are 16-byte aligned, one batch element of every tensor is below 2 GB and a second input starts on a
@@ -354,7 +356,7 @@ int rvsr_conv2d_backward_weight(const float* x1, int C1, const float* x2, int C2
 /* conv_wgrad_plan's answer for that call, without running it (no GPU needed, nothing launched, no pointer dereferenced): the arguments
  * of rvsr_conv2d_backward_weight that the plan looks at, the same validation and return code, and plan[4] = {family in the order of
  * ConvWgradFamily (0 vector ALU, 1 conv_wgrad2, 2 conv_wgrad5, 3 exact f32 5x5, 4 conv_wgrad1x1s, 5 conv_wgrad1x1, 6 exact f32 3x3,
- * 7 conv_wgrad_s2, 8 exact f32 3x3 stride 2, 9 exact f32 1x1), partial sums P, grid y, grid z}.  The workspace the call needs is
+ * 7 conv_wgrad_s2, 8 exact f32 3x3 stride 2, 9 exact f32 1x1, 10 exact f32 7x7), partial sums P, grid y, grid z}.  The workspace the call needs is
  * rvsr_conv2d_wgrad_workspace_bytes >= 4 * P * (Co * (C1 + C2) * k * k + Co) bytes. */
 int rvsr_conv2d_backward_weight_plan(const float* x1, int C1, const float* x2, int C2, int Hin, int Win,
                                      const float* gout, const float* gact, float gact_slope, int g_mode,
@@ -607,6 +609,36 @@ int rvsr_prelu_backward(const float* g, const float* a, const float* b /*NULL ok
  * gradient.  n == 0 is RVSR_ERR_BAD_ARG. */
 int rvsr_prelu_plan(size_t n, const void* f0, const void* f1, const void* f2, const void* f3, const void* f4, const void* keep,
                     RVSR_HOST int* vec, RVSR_HOST int* blocks);
+
+/* ---------------------------------------------------------------------------------------------
+ * 10. TOF: the resampling operators of SpyNet (codes/models/archs/TOF_arch.py:54-88, arch_util.py:47-80)
+ * --------------------------------------------------------------------------------------------- */
+
+/* arch_util.flow_warp (arch_util.py:47-80; called at TOF_arch.py:84 per pyramid level and :87 at full resolution):
+ *   out[b,c,y,x] = grid_sample(x, align_corners=True) at (x + flow[b,y,x,0], y + flow[b,y,x,1])
+ * x, out, gout, gx (B,C,H,W); flow, gflow (B,H,W,2) in pixels, x first; all f32, contiguous.
+ * The sampling coordinate is w + fx (h + fy) in one float32 addition.  The reference normalises, g = 2 (w + fx) / max(W - 1, 1) - 1, and
+ * grid_sample un-normalises, (g + 1) / 2 * (W - 1): that round trip is the same number up to two or three ulps and is left out on
+ * purpose, so that a zero flow is the identity and an integer flow a shift, bit for bit.  An axis of one pixel samples coordinate 0
+ * whatever the flow, with flow gradient 0 (what the round trip gives: it multiplies by W - 1 = 0).
+ * interp 0: bilinear, 1: nearest (round half to even).  padding 0: zeros, 1: border.  Anything else (reflection) is RVSR_ERR_UNSUPPORTED.
+ * Backward: gflow (NULL = skip) is gathered, one thread per pixel over the channels -- no atomics, bit-identical from run to run; it is
+ * zero for nearest, and under border for a coordinate on or beyond the frame's edge (<= 0 or >= W - 1, as grid_sample clips).  gx (NULL = skip) is scattered with float atomic adds INTO what the
+ * buffer holds (the caller zero-fills it): order-dependent in its last bits.  x may be NULL when gflow is. */
+int rvsr_flow_warp_forward(const float* x, const float* flow, float* out, int B, int C, int H, int W, int interp, int padding,
+                           void* stream);
+int rvsr_flow_warp_backward(const float* gout, const float* x /*NULL ok without gflow*/, const float* flow, float* gx /*NULL ok*/,
+                            float* gflow /*NULL ok*/, int B, int C, int H, int W, int interp, int padding, void* stream);
+
+/* F.avg_pool2d(x, 2, 2) (the image pyramids, TOF_arch.py:66-76): in `planes` images of HxW -> out of (H/2)x(W/2), sizes floor; an odd
+ * last row or column takes no part and gets zero gradient.  A frame of one row or column pools to nothing (no launch). */
+int rvsr_avgpool2_forward(const float* in, float* out, size_t planes, int H, int W, void* stream);
+int rvsr_avgpool2_backward(const float* gout, float* gin, size_t planes, int H, int W, void* stream);
+
+/* scale * F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) (the flow between pyramid levels, TOF_arch.py:81-82):
+ * source coordinate dst * (H - 1) / (2H - 1), 0 for H == 1.  The backward is a gather in a fixed order (no atomics). */
+int rvsr_upsample2_ac_forward(const float* in, float* out, size_t planes, int H, int W, float scale, void* stream);
+int rvsr_upsample2_ac_backward(const float* gout, float* gin, size_t planes, int H, int W, float scale, void* stream);
 
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);

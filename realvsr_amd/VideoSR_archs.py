@@ -1,7 +1,8 @@
-"""define_G for the generators on the MI355X path (codes/models/VideoSR_archs.py:18-58: EDVR / EDVR_NoUp / TDAN / RCAN / FSTRN branches)."""
-from .archs import EDVR_arch, FSTRN_arch, RCAN_arch, TDAN_arch
+"""define_G for the generators on the MI355X path (codes/models/VideoSR_archs.py:18-58: EDVR / EDVR_NoUp / TDAN / RCAN / FSTRN / TOF branches)."""
+from .archs import EDVR_arch, FSTRN_arch, RCAN_arch, TDAN_arch, TOF_arch
 
 _FSTRN_KEYS = ('k', 'nf', 'nframes')
+_TOF_KEYS = ('nframes', 'K', 'nc', 'nf', 'nb')
 _RCAN_KEYS = ('num_in_ch', 'num_out_ch', 'num_frames', 'num_feat', 'num_group', 'num_block', 'squeeze_factor', 'res_scale')
 
 
@@ -32,6 +33,13 @@ def define_G(opt):
         if missing:
             raise NotImplementedError('Generator model [FSTRN]: network_G lacks ' + ', '.join(missing))
         return FSTRN_arch.FSTRN(k=opt_net['k'], nf=opt_net['nf'], nframes=opt_net['nframes'], scale=opt['scale'])
+    if which_model == 'TOF':
+        # as for RCAN: the reference reads these keys and opt['scale'] with [] and has no defaults for them
+        missing = [k for k in _TOF_KEYS if k not in opt_net] + ([] if 'scale' in opt else ['scale (in opt)'])
+        if missing:
+            raise NotImplementedError('Generator model [TOF]: network_G lacks ' + ', '.join(missing))
+        return TOF_arch.TOF(nframes=opt_net['nframes'], K=opt_net['K'], in_nc=opt_net['nc'], out_nc=opt_net['nc'], nf=opt_net['nf'],
+                            nb=opt_net['nb'], upscale=opt['scale'])
     raise NotImplementedError('Generator model [{:s}] not recognized'.format(which_model))
 
 

@@ -1,5 +1,5 @@
 """Hot-path subset of codes/models/archs/arch_util.py: initialize_weights (:8-25), make_layer
-(:28-39), ResidualBlock_noBN (:121-139).  Parameter names / init identical to the reference."""
+(:28-39), flow_warp (:47-80), ResidualBlock_noBN (:121-139).  Parameter names / init identical to the reference."""
 import torch.nn as nn
 import torch.nn.init as init
 
@@ -23,6 +23,13 @@ def initialize_weights(net_l, scale=1):
 
 def make_layer(basic_block, num_basic_block, **kwarg):
     return nn.Sequential(*[basic_block(**kwarg) for _ in range(num_basic_block)])
+
+
+def flow_warp(x, flow, interp_mode='bilinear', padding_mode='zeros'):
+    """Warp x (n, c, h, w) with the optical flow (n, h, w, 2), in pixels (:47-80): one HIP operator instead of the mesh grid, its
+    normalisation and F.grid_sample(align_corners=True).  'reflection' padding is not built."""
+    assert x.size()[-2:] == flow.size()[1:3]
+    return RF.flow_warp(x, flow, interp_mode, padding_mode)
 
 
 class ResidualBlock_noBN(nn.Module):

@@ -120,6 +120,8 @@ class PackedWeights:
         """Packed image tensor for (weight, kind, geometry), or None when the weight is not cacheable."""
         if not self.enabled or _lib.get_gemm_mode() == 'f32':
             return None
+        if kind == 'conv' and k == 7:   # exact-f32 kernels in every GEMM mode: no image exists, and repack() never sees these weights
+            return None
         if getattr(weight, '_rvsr_grad_home', None) is None and getattr(weight, '_rvsr_parent', None) is None:
             return None
         key = (id(weight), kind, C_in, Co, k, w_mode)

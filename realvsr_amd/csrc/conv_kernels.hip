@@ -272,6 +272,7 @@ static int launch_fwd(const ConvFwdParams& p, const ConvFwdPlan& q, int ksize, i
     ROW(5, 1, 8, 4);
     ROW(5, 2, 4, 4);
     ROW(1, 1, 32, 32);
+    ROW(7, 1, 4, 2);
 #undef ROW
     return rvsr_conv_launch("conv_fwd", k, dim3(q.gx, q.gy, q.gz), RVSR_WG, q.lds, st, p);
 }
@@ -310,8 +311,8 @@ static int conv_fwd_params(ConvFwdParams& p, const float* x1, int C1, const floa
     if (addend_period < 0 || (addend_period > 0 && !residual)) FAIL(RVSR_ERR_BAD_ARG, "conv2d: addend period %d without an addend", addend_period);
     if ((x2 == nullptr) != (C2 == 0) || (out2 == nullptr) != (Co2 == 0))
         FAIL(RVSR_ERR_BAD_ARG, "conv2d: second input/output pointer and channel count disagree");
-    if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 or 5 supported)", ksize);
-    if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: stride %d", stride);
+    if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3, 5 or 7 supported)", ksize);
+    if (stride != 1 && !(stride == 2 && ksize != 1 && ksize != 7)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: stride %d", stride);
     if (in_mode != 0 && (x2 != nullptr || stride != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: view mode with concat/stride");
     if (xact && x2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d: act' fusion with concat input");
     // (an addend with a split or pixel-shuffled output is the plan's to refuse, silently: the caller has a plan B)
@@ -428,6 +429,7 @@ extern "C" void rvsr_set_gemm_mode(int mode) { rvsr_g_gemm_mode = (mode >= 0 && 
 extern "C" void rvsr_set_gemm_mode_thread(int mode) { rvsr_t_gemm_mode = (mode >= 0 && mode <= 3) ? mode : -1; }
 extern "C" int rvsr_get_gemm_mode() { return rvsr_gemm_mode_now(); }
 extern "C" size_t rvsr_conv2d_forward_workspace_bytes(int C1, int C2, int Co, int ksize) {
+    if (ksize == 7) return 0;   // (exact-f32 family only: it reads the weights where they are, no packed image)
     return rvsr_conv_fwd2_workspace_bytes(ksize, Co, C1 + C2);
 }
 
@@ -449,8 +451,8 @@ static int conv_wgrad_params(ConvWgradParams& p, const float* x1, int C1, const 
                              int ksize, int stride, int Hout, int Wout) {
     if (!x1 || !gout || !grad_weight || B <= 0) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: null/empty argument");
     if ((x2 == nullptr) != (C2 == 0)) FAIL(RVSR_ERR_BAD_ARG, "conv2d_backward_weight: x2/C2 disagree");
-    if (ksize != 1 && ksize != 3 && ksize != 5) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: kernel size %d", ksize);
-    if (stride != 1 && !(stride == 2 && ksize != 1)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: stride %d", stride);
+    if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: kernel size %d", ksize);
+    if (stride != 1 && !(stride == 2 && ksize != 1 && ksize != 7)) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: stride %d", stride);
     if (g_mode != 0 && g_mode != 2) FAIL(RVSR_ERR_UNSUPPORTED, "conv2d_backward_weight: gradient view mode %d", g_mode);
     make_view(p.x.a, x1, nullptr, 0.f, C1, Hin, Win, 0, 0, 0);
     make_view(p.x.b, x2, nullptr, 0.f, C2, Hin, Win, 0, 0, 0);
@@ -518,6 +520,7 @@ extern "C" int rvsr_conv2d_backward_weight(const float* x1, int C1, const float*
         case CONV_WGRAD_S2: rc = rvsr_launch_conv_wgrad_s2(p, q.gy, q.gz, st); break;
         case CONV_WGRAD_F32_3S2: rc = launch_wgrad<3, 2, 32>(p, q.gy, q.gz, st); break;
         case CONV_WGRAD_F32_1: rc = launch_wgrad<1, 1, 64>(p, q.gy, q.gz, st); break;
+        case CONV_WGRAD_F32_7: rc = launch_wgrad<7, 1, 8>(p, q.gy, q.gz, st); break;
     }
     if (rc) return rc;
     rvsr_launch_reduce(p.part, p.P, nw, grad_weight, accumulate, st, p.bpart, (size_t)Co, grad_bias);

@@ -96,7 +96,8 @@ static inline ConvFwdPlan conv_fwd_plan(const ConvFwdParams& p, int ksize, int s
     if (!split && !thin) {
         // GEMM mode 1 is exact f32 everywhere; 5x5 through the zero-insert view of a stride-2 data gradient (in_mode 1) is staged by
         // the 3x3 kernels only; conv_fwd5's scalar staging wants a second input behind a multiple of 8 channels
-        split = gemm_mode != 1 && (va.mode != 1 || ksize == 3) && (vb.C == 0 || va.C % 8 == 0);
+        // (7x7, SpyNet's blocks: no bf16-split kernel exists for it, the exact-f32 family in every GEMM mode)
+        split = gemm_mode != 1 && ksize != 7 && (va.mode != 1 || ksize == 3) && (vb.C == 0 || va.C % 8 == 0);
         // conv_fwd2 stages a plain view through raw buffer loads: 32-bit byte offsets inside one batch element (< 2 GB), and a second
         // input only behind a whole chunk, a multiple of 16 (1x1: 32) channels
         if (split && (ksize != 3 || stride == 2) && va.mode == 0 &&
@@ -120,6 +121,7 @@ static inline ConvFwdPlan conv_fwd_plan(const ConvFwdParams& p, int ksize, int s
         q.mt = p.Co <= 32 ? 1 : (p.Co <= 64 ? 2 : 4);
         const int wide_m = q.mt == 4;   // (chunk sizes: LDS of 5x5 stride 1 66 / 58 KB, 2 workgroups per CU; stride 2 34 / 46 / 72 KB)
         q.cc = ksize == 1 ? 32 : ksize == 3 ? (stride == 1 ? (wide_m ? 8 : 16) : (wide_m ? 4 : 8)) : (stride == 1 ? (wide_m ? 4 : 8) : 4);
+        if (ksize == 7) q.cc = wide_m ? 2 : 4;   // (14 x 38 halo, 49-tap weight slice: 59.5 / 54.8 KB at MT <= 2 / 4, 2 workgroups per CU; CC even)
         const int IH = 7 * stride + ksize, IW = 31 * stride + ksize;
         q.lds = sizeof(float) * ((size_t)q.cc * IH * IW + (size_t)T * q.cc * (q.mt * 32 + 1));
         q.gx = (unsigned)(ntx * nty8);
@@ -187,6 +189,7 @@ enum ConvWgradFamily {
     CONV_WGRAD_S2,         // conv_wgrad_s2_kernel: 3x3 / stride 2 on the bf16 matrix cores
     CONV_WGRAD_F32_3S2,    // conv_wgrad_kernel<3, 2, 32>
     CONV_WGRAD_F32_1,      // conv_wgrad_kernel<1, 1, 64>
+    CONV_WGRAD_F32_7,      // conv_wgrad_kernel<7, 1, 8>: 7x7 / stride 1 in every GEMM mode (SpyNet's blocks)
     CONV_WGRAD_FAMILIES
 };
 struct ConvWgradPlan {
@@ -200,6 +203,7 @@ static inline bool conv_wgrad_can(int family, int ksize, int stride, int Co) {
         case CONV_WGRAD2: case CONV_WGRAD_F32_3S1: return ksize == 3 && stride == 1;
         case CONV_WGRAD5: case CONV_WGRAD_F32_5: return ksize == 5;
         case CONV_WGRAD_S2: case CONV_WGRAD_F32_3S2: return ksize == 3 && stride == 2;
+        case CONV_WGRAD_F32_7: return ksize == 7 && stride == 1;
         default: return ksize == 1;   // CONV_WGRAD_1X1S, CONV_WGRAD_1X1, CONV_WGRAD_F32_1
     }
 }
@@ -220,6 +224,9 @@ static inline ConvWgradPlan conv_wgrad_slicing(int family, int B, int Hout, int 
             break;
         case CONV_WGRAD_F32_5:  // 16 input channels per workgroup = 400 GEMM columns, 7 accumulator tiles per wave (64 would need 25)
             gz = (Ctot + 15) / 16;
+            break;
+        case CONV_WGRAD_F32_7:  // 8 input channels per workgroup = 392 GEMM columns, 13 tiles, 7 per wave: the registers of <5, S, 16>
+            gz = (Ctot + 7) / 8;
             break;
         case CONV_WGRAD_S2:     // 2 workgroups of 4 waves per CU, pixels cut into 16-pixel units
             units = (long)B * Hout * ((Wout + 15) / 16);

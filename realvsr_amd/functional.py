@@ -152,7 +152,8 @@ def _conv(x1, weight, out1, *, what, x2=None, xact=None, xact_slope=0.0, in_mode
     # 'f16fp8' mode (_lib.set_gemm_mode): every forward conv the library's plan grants the f16 + fp8 product format (weight image and kernel)
     if _lib.fmt_f16fp8() and L.rvsr_conv2d_forward_plan(*call, w_mode | 4, *tail, None) == 0:
         w_mode |= 4
-    # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused)
+    # (5x5 through the zero-insert view: the exact-f32 kernel reads the weights directly, an image would go unused; 7x7 has no image at
+    # all, which PackedWeights.get knows)
     buf = None if k == 5 and in_mode == 1 else packed_weights.get(weight, 'conv', C1 + C2, Co1 + Co2, k, w_mode, nbytes)
     if buf is not None:
         ws, w_mode = buf, w_mode | 2
@@ -1829,6 +1830,105 @@ def conv_transpose1x1(x, convt):
         raise NotImplementedError('conv_transpose1x1: kernel %s / stride %s; only kernel 1, stride 1 is on the MI355X path'
                                   % (tuple(convt.kernel_size), tuple(convt.stride)))
     return _ConvT1x1.apply(x, convt.weight, convt.bias)
+
+
+# ------------------------------------------------------------------------------------------ TOF: SpyNet's resampling operators
+_WARP_INTERP = {'bilinear': 0, 'nearest': 1}
+_WARP_PADDING = {'zeros': 0, 'border': 1}
+
+
+class _FlowWarp(Function):
+    """arch_util.flow_warp: grid_sample(align_corners=True) of x (B, C, H, W) at pixel + flow (B, H, W, 2)."""
+
+    @staticmethod
+    def forward(ctx, x, flow, interp, padding):
+        _need_cuda(x, flow)
+        x, flow = x.contiguous(), flow.contiguous()
+        B, C, H, W = x.shape
+        if tuple(flow.shape) != (B, H, W, 2):
+            raise RuntimeError('flow_warp: x %s needs a flow of %s, got %s' % (tuple(x.shape), (B, H, W, 2), tuple(flow.shape)))
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().rvsr_flow_warp_forward(_p(x), _p(flow), _p(out), B, C, H, W, interp, padding, _stream()), 'flow_warp_forward')
+        ctx.cfg = (interp, padding)
+        ctx.save_for_backward(x, flow)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, flow = ctx.saved_tensors
+        interp, padding = ctx.cfg
+        B, C, H, W = x.shape
+        gout = gout.contiguous()
+        # either gradient is skipped when autograd wants none (TOF: the frames are data, gx is never needed); gx is accumulated atomically
+        gx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
+        gflow = torch.empty_like(flow) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().rvsr_flow_warp_backward(_p(gout), _p(x), _p(flow), _p(gx), _p(gflow), B, C, H, W, interp, padding, _stream()),
+                   'flow_warp_backward')
+        return gx, gflow, None, None
+
+
+def flow_warp(x, flow, interp_mode='bilinear', padding_mode='zeros'):
+    """F.grid_sample(x, normalised(pixel + flow), mode=interp_mode, padding_mode=padding_mode, align_corners=True): x (B, C, H, W), flow
+    (B, H, W, 2) in pixels, x first.  'bilinear' / 'nearest' with 'zeros' / 'border'.  The flow gradient is deterministic; the image
+    gradient is accumulated with float atomics (order-dependent in its last bits)."""
+    if interp_mode not in _WARP_INTERP:
+        raise NotImplementedError("flow_warp: interp_mode %r; 'bilinear' and 'nearest' are on the MI355X path" % (interp_mode,))
+    if padding_mode not in _WARP_PADDING:
+        raise NotImplementedError("flow_warp: padding_mode %r; 'zeros' and 'border' are on the MI355X path" % (padding_mode,))
+    return _FlowWarp.apply(x, flow, _WARP_INTERP[interp_mode], _WARP_PADDING[padding_mode])
+
+
+class _AvgPool2(Function):
+    @staticmethod
+    def forward(ctx, x):
+        _need_cuda(x)
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        out = x.new_empty(B, C, H // 2, W // 2)
+        _lib.check(_lib.lib().rvsr_avgpool2_forward(_p(x), _p(out), B * C, H, W, _stream()), 'avgpool2_forward')
+        ctx.cfg = (B, C, H, W)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        B, C, H, W = ctx.cfg
+        gout = gout.contiguous()
+        gin = gout.new_empty(B, C, H, W)
+        _lib.check(_lib.lib().rvsr_avgpool2_backward(_p(gout) if gout.numel() else None, _p(gin), B * C, H, W, _stream()), 'avgpool2_backward')
+        return gin
+
+
+def avg_pool2(x):
+    """F.avg_pool2d(x, 2, 2): sizes floor, an odd last row or column takes no part."""
+    return _AvgPool2.apply(x)
+
+
+class _Upsample2AC(Function):
+    @staticmethod
+    def forward(ctx, x, scale):
+        _need_cuda(x)
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        out = x.new_empty(B, C, 2 * H, 2 * W)
+        _lib.check(_lib.lib().rvsr_upsample2_ac_forward(_p(x), _p(out), B * C, H, W, scale, _stream()), 'upsample2_ac_forward')
+        ctx.cfg = (scale, B, C, H, W)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        scale, B, C, H, W = ctx.cfg
+        gout = gout.contiguous()
+        gin = gout.new_empty(B, C, H, W)
+        _lib.check(_lib.lib().rvsr_upsample2_ac_backward(_p(gout), _p(gin), B * C, H, W, scale, _stream()), 'upsample2_ac_backward')
+        return gin, None
+
+
+def upsample2_ac(x, scale=1.0):
+    """scale * F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True)"""
+    return _Upsample2AC.apply(x, float(scale))
 
 
 # ------------------------------------------------------------------------------------------ device guard
