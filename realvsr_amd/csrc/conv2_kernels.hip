@@ -18,23 +18,28 @@
 #include "conv_plan.h"
 
 #include "bf16x3.h"
+#include "timeline.h"
 
-// Energy ablations of scratch builds (tools/build_variant.sh conv2_kernels <name> -DRVSR_ABL5=<bits>; results wrong by construction; the 8 x 64
-// kernel runs at the package power cap, so its time follows the energy of what it does -- profiles/r05_notes.md): 1 = LDS fragment reads of
-// taps 2-8 dropped, 2 = output stores dropped, 4 = input loads dropped
-#ifdef RVSR_ABL5
-constexpr int ABL5 = RVSR_ABL5;
-#else
-constexpr int ABL5 = 0;
-#endif
-
-#ifdef RVSR_TIMELINE
-__device__ unsigned long long rvsr_dbg[512];
-extern "C" int rvsr_debug_read(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rvsr_dbg), sizeof(unsigned long long) * 512); }
-#define STAMP(i) do { if (blockIdx.x == 77 && tid == 0) rvsr_dbg[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#endif
+// Timeline slots (timeline.h) of conv_fwd5_kernel, workgroup 77; read by tools/conv_timeline.py.  Stage q of Q; `wave` = 0..7.
+// (The writers are named as macros, not as locals of the kernel: an unused local that reads blockIdx still moves instructions of the product build.)
+#define F5_TL_THREAD0 (blockIdx.x == 77 && threadIdx.x == 0)
+#define F5_TL_LANE0 (blockIdx.x == 77 && (threadIdx.x & 63) == 0)
+enum Fwd5Stamp {
+    F5_STAGE = 0,           // + 3 * (q & 7) + {1: stage start, 2: tap loop done, 3: closing barrier passed}, thread 0: the last 8 stages remain
+    F5_KERNEL_START = 60,   // thread 0, in front of the prologue
+    F5_KERNEL_END = 61,     // thread 0, behind the last stage
+    F5_Q3_LOOP_END = 70,    // + wave: stage Q - 3, tap loop done
+    F5_Q4_BARRIER = 80,     // + wave: stage Q - 4, closing barrier passed (the common release in front of stage Q - 3)
+    F5_Q4_LOOP_END = 90,    // + wave: stage Q - 4, tap loop done
+    F5_Q6 = 300,            // + 12 * wave + {0..8: start of tap, 9: tap loop done, 10: closing barrier passed, 11: the barrier in front, stage Q - 7}
+};
+// ... of conv_wgrad2_kernel, workgroup (77, 0, 0); read by tools/wgrad_timeline.py.  Tile ti = 0..5 of the workgroup's range.
+#define WG2_TL_THREAD0 (blockIdx.x == 77 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
+#define WG2_TL_LANE0 (blockIdx.x == 77 && blockIdx.y == 0 && blockIdx.z == 0 && (threadIdx.x & 63) == 0)
+enum Wgrad2Stamp {
+    WG2_T3_KSTEP = 120,     // + 10 * wave + {0..7: start of k-step, 8: k-steps done}, tile 3
+    WG2_TILE = 200,         // + 4 * ti + {0: top, 1: committed to LDS, 2: opening barrier passed, 3: MFMA phase (+ next tile's loads) done}, thread 0
+};
 
 // ------------------------------------------------------------------------------------------
 // Epilogue of the bf16x3 kernel: bias comes from LDS (staged once per tile), residual values are fetched in
@@ -222,7 +227,6 @@ __device__ __forceinline__ void conv2_epilogue_wide(f32x16 (&acc)[MT][2], const 
                     v.x *= resv[s].x > 0.f ? 1.f : p.slope; v.y *= resv[s].y > 0.f ? 1.f : p.slope;
                     v.z *= resv[s].z > 0.f ? 1.f : p.slope; v.w *= resv[s].w > 0.f ? 1.f : p.slope;
                 }
-                if (!(ABL5 & 2) || (m == 0 && rg == 0 && s == 0))   // (ABL5 & 2: one store in 16 kept so that the epilogue's arithmetic stays alive)
                 buf_store4(out_rs, off[s] + (unsigned)(o0 + m * 32 + 8 * rg + 4 * s) * HW4, 0u, v);
             }
         }
@@ -397,7 +401,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_fwd2_kernel(const ConvFwdPara
             acc[m][1] = zero16();
         }
         const int cx0 = x0, cy0 = y0, cmb = mb, cb_ = b;
-        STAMP(0);
         for (int chunk = 0; chunk < nchunks; ++chunk) {
             constexpr int NB = 3;
             if (!PF && STRIDE == 2) {   // batched: NB items in flight at a time
@@ -411,11 +414,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_fwd2_kernel(const ConvFwdPara
                 if (!PF) issue_loads(chunk);
                 commit_to_lds(chunk);
             }
-            STAMP(1 + chunk * 5);
             __syncthreads();
-            STAMP(2 + chunk * 5);
             if (PF && chunk + 1 < nchunks) issue_loads(chunk + 1);
-            STAMP(3 + chunk * 5);
 #pragma unroll
             for (int tap = 0; tap < T; ++tap) {
                 const int dy = tap / KS, dx = tap % KS;
@@ -448,9 +448,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_fwd2_kernel(const ConvFwdPara
                         for (int n = 0; n < 2; ++n) acc[m][n] = mfma_bf16(al[m], bh[n], acc[m][n]);
                 }
             }
-            STAMP(4 + chunk * 5);
             __syncthreads();
-            STAMP(5 + chunk * 5);
         }
         if (p.ps)
             conv2_epilogue<MT, 3>(acc, p, bias_s, cb_, cmb * MP, cy0 + wave * 2, cx0 + lo, hi);
@@ -463,13 +461,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_fwd2_kernel(const ConvFwdPara
             if (p.vec4) conv2_epilogue_v4<MT, 0>(acc, p, bias_s, cb_, cmb * MP, cy0 + wave * 2, cx0, lo, hi);
             else conv2_epilogue<MT, 0>(acc, p, bias_s, cb_, cmb * MP, cy0 + wave * 2, cx0 + lo, hi);
         }
-        STAMP(30);
         if (S + nwq < range1) {  // the stores above are asynchronous: the next tile's loads go out right behind them
             decode(S + nwq);
             tile_views();
             if (PF) issue_loads(0);
         }
-        STAMP(31);
         // bias_s of this tile is read by the epilogue above and rewritten by the next tile's chunk-0 commit:
         // that commit is followed by a barrier before any MFMA, and every wave passed the last barrier of this
         // tile before its epilogue; a wave still in its epilogue while another already commits the next tile
@@ -830,7 +826,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
         issue_loads(itile, ch, wsel, xsel);
     };
 
-    STAMP(60);
+    RVSR_STAMP(F5_TL_THREAD0, F5_KERNEL_START);
     stage_tile(0, 0, 0);
     issue_stage(0, 0, -1, -1);
     commit(0, -1, -1);
@@ -847,7 +843,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
         acc[m][1] = zero16();
     }
     for (int q = 0; q < Q; ++q) {
-        STAMP(1 + (q & 7) * 3);
+        RVSR_STAMP(F5_TL_THREAD0, F5_STAGE + 3 * (q & 7) + 1);
         const int buf = q & 1;
         const bf16x8* xs_hi = xs_base + buf * 2 * NX;
         const bf16x8* xs_lo = xs_hi + NX;
@@ -873,9 +869,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
 #pragma unroll
         for (int tap = 0; tap < T; ++tap) {
             const int sl = tap & 1;
-#ifdef RVSR_TIMELINE
-            if (blockIdx.x == 77 && lane == 0 && q == Q - 6) rvsr_dbg[300 + wave * 12 + tap] = __builtin_amdgcn_s_memtime();
-#endif
+            RVSR_STAMP(F5_TL_LANE0 && q == Q - 6, F5_Q6 + 12 * wave + tap);
             if (NT == 4) {
                 // f16 + fp8 format (NT == 4): the cross terms a1 * b2 + a2 * b1 of TWO taps in one 64-deep fp8 instruction (lane half 0 holds the
                 // a1 / b2 * 2^12 pieces, half 1 the a2 * 2^12 / b1 pieces: the E8M0 block scale of a lane's 32 k undoes the 2^12), issued
@@ -912,7 +906,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
                         }
                 }
             } else {
-            if (tap + 1 < ((ABL5 & 1) ? 2 : T)) fetch(tap + 1, sl ^ 1);   // (ABL5 & 1: fragments of taps 0 and 1 reused for taps 2-8)
+            if (tap + 1 < T) fetch(tap + 1, sl ^ 1);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -939,16 +933,14 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
             } else {
                 if (pub) commit(buf ^ 1, tap - 4, 8);
                 if (tap == 4) stage_tile(q + 2, k_nx2, c_nx2);
-                issue_stage(q + 2, c_nx2, tap - 4, (ABL5 & 4) ? 8 : VEC ? (tap < 6 ? tap - 4 : 8) : (tap - 4 < NIT ? tap - 4 : 8));   // (ABL5 & 4: no input loads after the first stages)
+                issue_stage(q + 2, c_nx2, tap - 4, VEC ? (tap < 6 ? tap - 4 : 8) : (tap - 4 < NIT ? tap - 4 : 8));
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP(2 + (q & 7) * 3);
-#ifdef RVSR_TIMELINE
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 3) rvsr_dbg[70 + wave] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 4) rvsr_dbg[90 + wave] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 6) rvsr_dbg[300 + wave * 12 + 9] = __builtin_amdgcn_s_memtime();
-#endif
+        RVSR_STAMP(F5_TL_THREAD0, F5_STAGE + 3 * (q & 7) + 2);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 3, F5_Q3_LOOP_END + wave);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 4, F5_Q4_LOOP_END + wave);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 6, F5_Q6 + 12 * wave + 9);
         const int k = k_cur;
         const bool last_chunk = c_cur == nchunks - 1;
         if (++c_cur == nchunks) { c_cur = 0; ++k_cur; }
@@ -979,17 +971,12 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
             }
         }
         __syncthreads();
-        STAMP(3 + (q & 7) * 3);
-#ifdef RVSR_TIMELINE
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 4) rvsr_dbg[80 + wave] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 6) rvsr_dbg[300 + wave * 12 + 10] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 77 && lane == 0 && q == Q - 7) rvsr_dbg[300 + wave * 12 + 11] = __builtin_amdgcn_s_memtime();
-#endif
+        RVSR_STAMP(F5_TL_THREAD0, F5_STAGE + 3 * (q & 7) + 3);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 4, F5_Q4_BARRIER + wave);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 6, F5_Q6 + 12 * wave + 10);
+        RVSR_STAMP(F5_TL_LANE0 && q == Q - 7, F5_Q6 + 12 * wave + 11);
     }
-    STAMP(61);
-#ifdef RVSR_TIMELINE
-    if (blockIdx.x == 77 && tid == 0) rvsr_dbg[62] = (unsigned long long)Q;
-#endif
+    RVSR_STAMP(F5_TL_THREAD0, F5_KERNEL_END);
 }
 
 
@@ -1170,11 +1157,6 @@ __device__ __forceinline__ void wg2_row(const unsigned char* xs_hi, const unsign
     }
 }
 
-// The X-row ring of round 4 (tile rows fastest, the two rows shared with the upper neighbour kept in LDS) measured no gain and is compiled out;
-// scratch builds: -DWGRAD2_RING=1 (and p.ring = 1 in conv_kernels.hip).
-#ifndef WGRAD2_RING
-#define WGRAD2_RING 0
-#endif
 template <bool ACT, int GMODE, int NT = 3>
 __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvWgradParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1229,7 +1211,7 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
                                    : (unsigned)((((o >> 2) * 2 * H) + 2 * row + ((o >> 1) & 1)) * (2 * W) + 16 * q));
     }
     const bool sec = c0 >= C1;              // (uniform) this workgroup's 64 channels come from the second input
-    int x_row[NXI], x_gx[NXI], x_lds[NXI];   // (x_lds: LDS offset of the item WITHOUT its row term; the row slot is a ring, see below)
+    int x_row[NXI], x_gx[NXI], x_lds[NXI];   // (image row / column relative to the tile's first pixel; LDS byte offset, -1: no item)
 #pragma unroll
     for (int i = 0; i < NXI; ++i) {
         const int it_raw = tid + i * WG2_THREADS;
@@ -1240,38 +1222,26 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
         const int c = c0 + cl;
         x_row[i] = row - 1;
         x_gx[i] = 8 * q - 4;
-        x_lds[i] = live ? cl * WG2_XP + q * 16 : -1;
+        x_lds[i] = live ? cl * WG2_XP + row * 80 + q * 16 : -1;
         // relative to a view that starts one row and four pixels BEFORE the image (so that row -1 / column -4 are offset >= 0)
         x_vo[i] = live && c < Ctot ? 4u * (unsigned)(((sec ? c - C1 : c) * H + row) * W + 8 * q) : OOB;
     }
     const size_t img_g = (size_t)p.Co * H * W;  // elements per image of G (same count for the pixel-shuffled storage)
     const size_t img_x1 = (size_t)C1 * H * W, img_x2 = (size_t)(Ctot - C1) * H * W;
 
-    // `part` < 0: everything at once (prologue).  Otherwise part 0..7 = one eighth of the tile's loads: the main loop
-    // issues one part per k-step of the MFMA phase so the requests trickle out under the matrix work instead of as one
-    // burst in front of it (the burst took ~5.5 K cycles to issue: the memory pipeline back-pressures).
-    // parts 0-3: X item `part`; parts 4, 5: G item 0, 1; parts 6, 7: nothing.
-    // Tile walk.  p.ring: tile ROWS fastest -- consecutive tiles of a workgroup are vertical neighbours, and of the six X rows a
-    // 4-row tile needs (y0 - 1 .. y0 + 4) the first two are the last two of the tile above: they stay in LDS (the row slots form a
-    // ring of six, rotated by four per tile) and only four rows are fetched -- X traffic 1.25x instead of 1.875x the tile's pixels,
-    // 73 instead of 93 KB per tile (the kernel moves as fast as its loads issue, profiles/r03_notes.md).  `fresh`: first tile of a
-    // column (or of the workgroup's range): all six rows are fetched.
-    struct TilePos { int b, y0, x0; bool fresh; };
+    // Tile walk: a workgroup's tiles are consecutive in (batch element, tile row, tile column) order, columns fastest.  Every tile fetches
+    // its whole X footprint -- the six rows y0 - 1 .. y0 + 4 by the 40 columns x0 - 4 .. x0 + 35, tile row r at LDS row r -- for its 4 x 32
+    // pixels: the X traffic is 240 / 128 = 1.875x the tile's pixels, 93 KB per tile with the G tile, and the kernel moves as fast as its loads
+    // issue (profiles/r03_notes.md).  A ring of row slots that kept the two rows shared with the tile above in LDS (1.25x) was tried in round 4
+    // and measured no gain (profiles/r04_notes.md).
+    struct TilePos { int b, y0, x0; };
     auto tile_pos = [&](int tile) {
         TilePos t;
         t.b = tile / (p.nty * p.ntx);
         const int trem = tile - t.b * (p.nty * p.ntx);
-        if (WGRAD2_RING && p.ring) {
-            const int tx = trem / p.nty, ty = trem - tx * p.nty;
-            t.y0 = ty * 4;
-            t.x0 = tx * 32;
-            t.fresh = ty == 0;
-        } else {
-            const int ty = trem / p.ntx;
-            t.y0 = ty * 4;
-            t.x0 = (trem - ty * p.ntx) * 32;
-            t.fresh = true;
-        }
+        const int ty = trem / p.ntx;
+        t.y0 = ty * 4;
+        t.x0 = (trem - ty * p.ntx) * 32;
         return t;
     };
     typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -1279,6 +1249,10 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
         const f32x4v q = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)so, 0));
         return make_float4(q.x, q.y, q.z, q.w);
     };
+    // `part` < 0: everything at once (prologue).  Otherwise part 0..7 = one eighth of the tile's loads: the main loop
+    // issues one part per k-step of the MFMA phase so the requests trickle out under the matrix work instead of as one
+    // burst in front of it (the burst took ~5.5 K cycles to issue: the memory pipeline back-pressures).
+    // parts 0-3: X item `part`; parts 4, 5: G item 0, 1; parts 6, 7: nothing.
     auto issue_loads = [&](const TilePos& tp, int part) {
         const int b = tp.b;
         int y0 = tp.y0, x0 = tp.x0;
@@ -1311,7 +1285,7 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
             for (int i = 0; i < NXI; ++i) {
                 if (part >= 0 && part != i) continue;
                 const int gy = y0 + x_row[i], gx = x0 + x_gx[i];
-                const bool ok = gy >= 0 && gy < H && (tp.fresh || x_row[i] >= 1);   // (rows y0 - 1, y0 of a non-fresh tile are in LDS already)
+                const bool ok = gy >= 0 && gy < H;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
                     const int gxx = gx + 4 * kk;
@@ -1321,7 +1295,7 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
         }
     };
 
-    auto commit = [&](bool fresh, int rbase) {
+    auto commit = [&]() {
 #pragma unroll
         for (int i = 0; i < NGI; ++i) {
             const int ol = g_o[i] - mb * 64;
@@ -1363,7 +1337,7 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
         }
 #pragma unroll
         for (int i = 0; i < NXI; ++i) {
-            if (x_lds[i] < 0 || (!fresh && x_row[i] < 1)) continue;
+            if (x_lds[i] < 0) continue;
             float v[8];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -1372,11 +1346,8 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
             }
             bf16x8 h8, l8;
             split8(v, h8, l8);
-            int slot = x_row[i] + 1 + rbase;          // ring slot of the item's row
-            slot = slot >= 6 ? slot - 6 : slot;
-            const int dst = x_lds[i] + slot * 80;
-            *reinterpret_cast<bf16x8*>(xs_hi + dst) = h8;
-            if (NT >= 2) *reinterpret_cast<bf16x8*>(xs_lo + dst) = l8;
+            *reinterpret_cast<bf16x8*>(xs_hi + x_lds[i]) = h8;
+            if (NT >= 2) *reinterpret_cast<bf16x8*>(xs_lo + x_lds[i]) = l8;
         }
     };
 
@@ -1384,32 +1355,21 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
     const int ntiles = p.B * p.nty * p.ntx;
     const int per = (ntiles + p.P - 1) / p.P;
     const int t_begin = blockIdx.x * per, t_end = t_begin + per < ntiles ? t_begin + per : ntiles;
-    TilePos cur_pos = tile_pos(t_begin < t_end ? t_begin : 0);
-    cur_pos.fresh = true;                   // (the first tile of the range has no predecessor in LDS)
-    if (t_begin < t_end) issue_loads(cur_pos, -1);
-    int rbase = 0;                          // ring slot of the tile's row y0 - 1
+    if (t_begin < t_end) issue_loads(tile_pos(t_begin), -1);
     for (int tile = t_begin; tile < t_end; ++tile) {
-        TilePos next_pos = tile_pos(tile + 1 < t_end ? tile + 1 : tile);
-        if (tile + 1 >= t_end) next_pos.fresh = true;   // (the re-read of the last tile: everything, nothing is committed)
+        const TilePos next_pos = tile_pos(tile + 1 < t_end ? tile + 1 : tile);   // (after the last tile: that tile again, nothing is committed)
         const int ti = tile - t_begin;
-        rbase = cur_pos.fresh ? 0 : (rbase + 4 >= 6 ? rbase - 2 : rbase + 4);
-        int roff[6];                        // LDS byte offset of tile row r (image row y0 - 1 + r)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) roff[r] = (r + rbase >= 6 ? r + rbase - 6 : r + rbase) * 80;
-        if (ti < 6) STAMP(200 + ti * 5);
-        commit(cur_pos.fresh, rbase);
-        if (ti < 6) STAMP(201 + ti * 5);
+        RVSR_STAMP(WG2_TL_THREAD0 && ti < 6, WG2_TILE + 4 * ti + 0);
+        commit();
+        RVSR_STAMP(WG2_TL_THREAD0 && ti < 6, WG2_TILE + 4 * ti + 1);
         __syncthreads();
-        if (ti < 6) STAMP(202 + ti * 5);
-        if (ti < 6) STAMP(203 + ti * 5);
+        RVSR_STAMP(WG2_TL_THREAD0 && ti < 6, WG2_TILE + 4 * ti + 2);
         const bool more = tile + 1 < t_end;
         if (!m_live && more) issue_loads(next_pos, -1);
         if (m_live) {
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
-#ifdef RVSR_TIMELINE
-                if (blockIdx.x == 77 && blockIdx.z == 0 && lane == 0 && ti == 3) rvsr_dbg[120 + wave * 10 + ks] = __builtin_amdgcn_s_memtime();
-#endif
+                RVSR_STAMP(WG2_TL_LANE0 && ti == 3, WG2_T3_KSTEP + 10 * wave + ks);
                 if (GMODE != 2 || more) issue_loads(next_pos, ks);   // (unconditional for the plain view: after the last tile it re-reads that tile)
                 __builtin_amdgcn_sched_barrier(0);
                 const int row = ks >> 1, cb = (ks & 1) * 16 + 8 * hi;  // this lane's 8 pixels: row, cols cb..cb+7
@@ -1419,19 +1379,16 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
                 // X octet pair holding stored cols cb .. cb+15 (= image cols x0-4+cb ..); tap dx needs +3+dx
                 const int xbase = (chalf * 32 + lo) * WG2_XP + cb * 2;
                 if (!second) {  // taps (0,0) (0,1) (0,2) (1,0) (1,1)
-                    wg2_row<7, NT>(xs_hi, xs_lo, xbase + roff[row + 0], ah, al, acc + 0);
-                    wg2_row<3, NT>(xs_hi, xs_lo, xbase + roff[row + 1], ah, al, acc + 3);
+                    wg2_row<7, NT>(xs_hi, xs_lo, xbase + (row + 0) * 80, ah, al, acc + 0);
+                    wg2_row<3, NT>(xs_hi, xs_lo, xbase + (row + 1) * 80, ah, al, acc + 3);
                 } else {        // taps (1,2) (2,0) (2,1) (2,2)
-                    wg2_row<4, NT>(xs_hi, xs_lo, xbase + roff[row + 1], ah, al, acc + 0);
-                    wg2_row<7, NT>(xs_hi, xs_lo, xbase + roff[row + 2], ah, al, acc + 1);
+                    wg2_row<4, NT>(xs_hi, xs_lo, xbase + (row + 1) * 80, ah, al, acc + 0);
+                    wg2_row<7, NT>(xs_hi, xs_lo, xbase + (row + 2) * 80, ah, al, acc + 1);
                 }
             }
         }
-        cur_pos = next_pos;
-        if (ti < 6) STAMP(204 + ti * 5);
-#ifdef RVSR_TIMELINE
-        if (blockIdx.x == 77 && blockIdx.z == 0 && lane == 0 && ti == 3) rvsr_dbg[120 + wave * 10 + 8] = __builtin_amdgcn_s_memtime();
-#endif
+        RVSR_STAMP(WG2_TL_THREAD0 && ti < 6, WG2_TILE + 4 * ti + 3);
+        RVSR_STAMP(WG2_TL_LANE0 && ti == 3, WG2_T3_KSTEP + 10 * wave + 8);
         __syncthreads();
     }
 

@@ -470,7 +470,6 @@ static int conv_wgrad_params(ConvWgradParams& p, const float* x1, int C1, const 
     p.ntx = (Wout + 31) / 32;
     p.nty = (Hout + 3) / 4;
     p.P = 0;
-    p.ring = 0;   // (the X-row ring of conv_wgrad2 measured no gain, profiles/r04_notes.md: compiled out, WGRAD2_RING in conv2_kernels.hip)
     return RVSR_OK;
 }
 

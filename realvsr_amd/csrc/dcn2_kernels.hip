@@ -18,19 +18,6 @@
 //   offsets / mask are read exactly once, coalesced along W; sigmoid of the mask logits in-kernel.
 #include "bf16x3.h"
 #include "dcn_common.h"
-
-#ifdef RVSR_TIMELINE_DCN
-__device__ unsigned long long rvsr_dbg_dcn[256];
-extern "C" int rvsr_debug_read_dcn(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rvsr_dbg_dcn), sizeof(unsigned long long) * 256); }
-#define DSTAMP(i) do { if (blockIdx.x == 77 && blockIdx.z == 1 && threadIdx.x == 0) rvsr_dbg_dcn[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define DSTAMP_W(i) do { if (blockIdx.x == 7 && blockIdx.z == 1 && threadIdx.x == 0) rvsr_dbg_dcn[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define DSTAMP_W3(i) do { if (blockIdx.x == 7 && blockIdx.z == 1 && threadIdx.x == 0) rvsr_dbg_dcn[(i) + 20] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define DSTAMP(i) do {} while (0)
-#define DSTAMP_W(i) do {} while (0)
-#define DSTAMP_W3(i) do {} while (0)
-#endif
-
 #include "dcn_tile.h"
 #include "dcn_plan.h"
 
@@ -61,7 +48,6 @@ __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(cons
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = zero16();
 
-    DSTAMP(0);
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const int c0 = chunk * 16;
         const int cb8 = c0 + 8 * hi;              // first channel of this lane's octet
@@ -93,11 +79,8 @@ __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(cons
                 bias_s[tid] = (p.bias != nullptr && o < d.Co) ? p.bias[o] : 0.f;
             }
         }
-        DSTAMP(1 + chunk * 5);
         stage_x_tile<NT, 4, TR, TC>(xt, d, b, c0, ty0, tx0, tid);
-        DSTAMP(2 + chunk * 5);
         __syncthreads();
-        DSTAMP(3 + chunk * 5);
 
         const float4* xq0 = xt + (2 * hi) * NPOS;  // channels cb8..cb8+3
         const float4* xq1 = xq0 + NPOS;            // channels cb8+4..cb8+7
@@ -169,9 +152,7 @@ __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(cons
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(al[mt], bh, acc[mt]);
         }
-        DSTAMP(4 + chunk * 5);
         __syncthreads();
-        DSTAMP(5 + chunk * 5);
     }
 
     if (oy >= d.Ho) return;
@@ -189,7 +170,6 @@ __global__ __launch_bounds__(TH * 64, MT <= 2 ? 4 : 2) void dcn_fwd2_kernel(cons
             if (ok) p.out[((size_t)b * d.Co + oc) * hw + pix] = v;
         }
     }
-    DSTAMP(30);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -274,8 +254,6 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
 
     const int ntiles = d.B * p.nty * d.ntx;
     for (int tile = blockIdx.x; tile < ntiles; tile += p.P) {
-        const bool st_ = tile == blockIdx.x + 2 * p.P;  // third tile of this workgroup
-        if (st_) DSTAMP_W(160);
         const int b = tile / (p.nty * d.ntx);
         const int trem = tile - b * (p.nty * d.ntx);
         const int ty = trem / d.ntx, tx = trem - ty * d.ntx;
@@ -329,11 +307,8 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
                 gT[px * GP + ol] = o < d.Co ? tview_get(p.g, b, o, y0 + (px >> 5), x0 + (px & 31)) : 0.f;
             }
         }
-        if (st_) DSTAMP_W(161);
         stage_x_tile<NT, 2, TR, TC>(xt, d, b, c0, ty0, tx0, tid);
-        if (st_) DSTAMP_W(162);
         __syncthreads();
-        if (st_) DSTAMP_W(163);
         // column tile: item = (pixel, tap); 8 channels of the chunk share the sampling geometry.
         // (dy, dx, mask) of all of a thread's items are fetched first, unconditionally (clamped pixel).
         constexpr int NBI = (DCN_NPX * 9 + NT - 1) / NT;
@@ -350,7 +325,6 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
             b_dx[i] = offp[hw];
             b_m[i] = d.mask[(size_t)b * d.mask_bs + (size_t)(g * 9 + tap) * hw + pixc];
         }
-        if (st_) DSTAMP_W(164);
 #pragma unroll
         for (int i = 0; i < NBI; ++i) {
             const int it = tid + i * NT;
@@ -405,9 +379,7 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
 #pragma unroll
             for (int j = 0; j < 8; ++j) colT[px * CP + j * 9 + tap] = v[j];
         }
-        if (st_) DSTAMP_W(165);
         __syncthreads();
-        if (st_) DSTAMP_W(166);
 #pragma unroll 2
         for (int ks = 0; ks < 8; ++ks) {  // wave w: pixels 16w .. 16w+15
             const int px = wave * 16 + 2 * ks + hi;
@@ -419,9 +391,7 @@ __global__ __launch_bounds__(512, 2) void dcn_bwdw2_kernel(const DcnBwdW2Params 
                 if (m1_live) acc[1][n] = mfma32(a1, bv, acc[1][n]);
             }
         }
-        if (st_) DSTAMP_W(167);
         __syncthreads();
-        if (st_) DSTAMP_W(168);
     }
 
     const int q = blockIdx.x * 8 + wave;

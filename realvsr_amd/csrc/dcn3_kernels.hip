@@ -18,13 +18,17 @@
 #include "dcn_tile.h"
 #include "dcn_plan.h"
 
-#ifdef RVSR_TIMELINE_DCN
-__device__ unsigned long long rvsr_dbg_dcn3[256];
-extern "C" int rvsr_debug_read_dcn3(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rvsr_dbg_dcn3), sizeof(unsigned long long) * 256); }
-#define TSTAMP(i) do { if (blockIdx.x == 77 && blockIdx.z == 1 && threadIdx.x == 0) rvsr_dbg_dcn3[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TSTAMP(i) do {} while (0)
-#endif
+#include "timeline.h"
+
+// Timeline slots (timeline.h) of dcn_fwd3_kernel: thread 0 of workgroup (77, 0, 1); read by tools/dcn3_timeline.py
+#define F3_TL (blockIdx.x == 77 && blockIdx.y == 0 && blockIdx.z == 1 && threadIdx.x == 0)
+enum Fwd3Stamp {
+    F3_START = 0,
+    F3_CHUNK = 0,        // + 6 * chunk (< 4) + {1: loads issued, 3: x tile in LDS (both R = 3 only), 4: opening barrier passed, 5: 9 taps done, 6: closing barrier passed}
+    F3_EPILOGUE = 30,    // output stored
+    F3_C1_TAP_END = 40,  // + tap: chunk 1, MFMAs of the tap issued
+    F3_C1_TAP = 60,      // + 5 * tap + {0: tap start, 1: corner reads issued, 2: blend (+ far path) done, 3: split done}, chunk 1
+};
 
 // The x tile of a 16-channel chunk for an 8 x 32 pixel workgroup: 16 rows x 40 columns x 4 channel quads = 2560 float4
 // items = 5 per thread of a 512-thread workgroup.  Item decode is shifts and masks only and four of the five items
@@ -100,14 +104,6 @@ __device__ __forceinline__ f32x2 blend4(f32x2 s, f32x2 t, f32x2 a00, f32x2 a01, 
 // multiple of 4 for all three: tile rows start on 16-byte boundaries and the large tiles are staged with 16-byte loads.
 // TERMS: terms of the bf16 product (rvsr_common.h: gemm modes): 3 = hi*hi + hi*lo + lo*hi; 2 = without the weights' lo part (that half of
 // the weight slice is not fetched); 1 = hi*hi (no lo part of the column values either)
-// Timing ablations of scratch builds (tools/build_variant.sh dcn3_kernels <name> -DRVSR_ABL3=<bits>; results wrong by construction):
-// 1 no MFMAs (nor weight-fragment reads), 4 no corner reads, 8 no far path, 16 no blend / split, 32 no offset / mask requests,
-// 64 no staging (x tile loads + stores, weight DMA; the barriers stay)
-#ifdef RVSR_ABL3
-constexpr int ABL3 = RVSR_ABL3;
-#else
-constexpr int ABL3 = 0;
-#endif
 template <int MT, int R, int TERMS = 3>
 __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_kernel(const DcnFwdParams p, const bf16x8* __restrict__ wpack) {
     constexpr int TH = 8, NT = TH * 64;
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = zero16();
 
-    TSTAMP(0);
+    RVSR_STAMP(F3_TL, F3_START);
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const int c0 = chunk * 16;
         const int cb8 = c0 + 8 * hi;              // first channel of this lane's octet
@@ -160,8 +156,7 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
         const unsigned off_lane = 4u * (pixc + (unsigned)(dg * 18) * (unsigned)hw), msk_lane = 4u * (pixc + (unsigned)(dg * 9) * (unsigned)hw);
         const unsigned off_pl = 4u * (unsigned)(g0 * 18) * (unsigned)hw, msk_pl = 4u * (unsigned)(g0 * 9) * (unsigned)hw, pl = 4u * (unsigned)hw;
         float n_dy = buf_load(off_rs, off_lane, off_pl), n_dx = buf_load(off_rs, off_lane, off_pl + pl), n_m = buf_load(msk_rs, msk_lane, msk_pl);
-        if (ABL3 & 32) { n_dy = (float)lane * 1e-3f; n_dx = n_dy; n_m = 0.5f; }
-        if (!(ABL3 & 64) || chunk == 0) {   // weight slice + x tile of the chunk: ALL global loads first, then the LDS writes (one round trip)
+        {   // weight slice + x tile of the chunk: ALL global loads first, then the LDS writes (one round trip)
             // weight slice: LDS-DMA (global_load_lds_dwordx4: lane l of a wave lands at M0 + 16 l, so a linear copy needs
             // no registers, no ds_write and no wait before the barrier's)
             const bf16x8* src = wpack + ((size_t)mb * nchunks + chunk) * 2 * WVEC;
@@ -176,10 +171,9 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
                 static_assert(R != 3 || (TR == 16 && TC == 40 && NT == 512), "xtile16x40 is written for this tile");
                 XTile16x40 xr;
                 xtile16x40_load(xr, d, x_rs, c0, ty0, tx0, tid);
-                TSTAMP(1 + 6 * chunk);
-                TSTAMP(2 + 6 * chunk);
+                RVSR_STAMP(F3_TL && chunk < 4, F3_CHUNK + 6 * chunk + 1);
                 xtile16x40_commit(xt, xr, d, c0, tid);
-                TSTAMP(3 + 6 * chunk);
+                RVSR_STAMP(F3_TL && chunk < 4, F3_CHUNK + 6 * chunk + 3);
             } else {
                 // item = (quad, row, group of 4 columns): four 16-byte loads (one per channel of the quad) land as the float4s of four
                 // positions -- a renaming of registers, no shuffles.  Rows / column groups outside the image and channels beyond C read
@@ -225,16 +219,15 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the weight DMA of this wave has landed
         __syncthreads();
-        TSTAMP(4 + 6 * chunk);
+        RVSR_STAMP(F3_TL && chunk < 4, F3_CHUNK + 6 * chunk + 4);
 
         const float4* xq0 = xt + (2 * hi) * NPOS;  // channels cb8..cb8+3 (xq0[NPOS + pos]: cb8+4..cb8+7)
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            if (chunk == 1) TSTAMP(60 + 5 * tap);
+            RVSR_STAMP(F3_TL && chunk == 1, F3_C1_TAP + 5 * tap + 0);
             const float dy = n_dy, dx = n_dx;
             float m = n_m;
-            if (ABL3 & 32) { n_dy = (float)lane * 1e-3f; n_dx = n_dy; n_m = 0.5f; }
-            else if (tap < 8) {  // (compile-time) prefetch the next tap's offsets/mask under this tap's math
+            if (tap < 8) {  // (compile-time) prefetch the next tap's offsets/mask under this tap's math
                 n_dy = buf_load(off_rs, off_lane, off_pl + (unsigned)(2 * tap + 2) * pl);
                 n_dx = buf_load(off_rs, off_lane, off_pl + (unsigned)(2 * tap + 3) * pl);
                 n_m = buf_load(msk_rs, msk_lane, msk_pl + (unsigned)(tap + 1) * pl);
@@ -254,20 +247,15 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
             const f32x2 wy = {m - wy1, wy1};
             const f32x2 wt = wy * lx, wsd = wy - wt;
             const int pos = in_tile ? r0 * TC + s0 : 0;
-            float4 a00, b00, a01, b01, a10, b10, a11, b11;
-            if (ABL3 & 4) { a00 = make_float4(wsd.x, wsd.y, wt.x, wt.y); b00 = a01 = b01 = a10 = b10 = a11 = b11 = a00; }
-            else {
-                a00 = xq0[pos]; b00 = xq0[NPOS + pos]; a01 = xq0[pos + 1]; b01 = xq0[NPOS + pos + 1];
-                a10 = xq0[pos + TC]; b10 = xq0[NPOS + pos + TC]; a11 = xq0[pos + TC + 1]; b11 = xq0[NPOS + pos + TC + 1];
-            }
-            if (chunk == 1) TSTAMP(61 + 5 * tap);
+            const float4 a00 = xq0[pos], b00 = xq0[NPOS + pos], a01 = xq0[pos + 1], b01 = xq0[NPOS + pos + 1];
+            const float4 a10 = xq0[pos + TC], b10 = xq0[NPOS + pos + TC], a11 = xq0[pos + TC + 1], b11 = xq0[NPOS + pos + TC + 1];
+            RVSR_STAMP(F3_TL && chunk == 1, F3_C1_TAP + 5 * tap + 1);
             const f32x2 p0 = blend4(wsd, wt, lo2(a00), lo2(a01), lo2(a10), lo2(a11));
             const f32x2 p1 = blend4(wsd, wt, hi2(a00), hi2(a01), hi2(a10), hi2(a11));
             const f32x2 p2 = blend4(wsd, wt, lo2(b00), lo2(b01), lo2(b10), lo2(b11));
             const f32x2 p3 = blend4(wsd, wt, hi2(b00), hi2(b01), hi2(b10), hi2(b11));
             float v[8] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
-            if (ABL3 & 16) { v[0] = a00.x; v[1] = b00.x; v[2] = a01.x; v[3] = b01.x; v[4] = a10.x; v[5] = b10.x; v[6] = a11.x; v[7] = b11.x; }
-            if (!(ABL3 & 8) && !in_tile && oct_ok) {
+            if (!in_tile && oct_ok) {
                 // large offset: this lane gathers its corners from global memory, with the reference's rules spelled out
                 // (image coordinates; kernel.cu:467-497,618)
 #pragma unroll
@@ -295,42 +283,27 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
                         v[j] = cb8 + j < d.C ? u00 * q00[j] + u01 * q01[j] + u10 * q10[j] + u11 * q11[j] : 0.f;
                 }
             }
-            if (chunk == 1) TSTAMP(62 + 5 * tap);
+            RVSR_STAMP(F3_TL && chunk == 1, F3_C1_TAP + 5 * tap + 2);
             bf16x8 bh, bl;
-            if (ABL3 & 16) { bh = __builtin_bit_cast(bf16x8, make_float4(v[0], v[1], v[2], v[3])); bl = __builtin_bit_cast(bf16x8, make_float4(v[4], v[5], v[6], v[7])); }
-            else split8(v, bh, bl);
-            if (ABL3 & 1) { acc[0][0] += (float)bh[0] + (float)bl[1]; continue; }
-            if (chunk == 1) TSTAMP(63 + 5 * tap);
+            split8(v, bh, bl);
+            RVSR_STAMP(F3_TL && chunk == 1, F3_C1_TAP + 5 * tap + 3);
             bf16x8 ah[MT], al[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 ah[mt] = ws_hi[(tap * 2 + hi) * MP + mt * 32 + lo];
                 if (TERMS >= 3) al[mt] = ws_lo[(tap * 2 + hi) * MP + mt * 32 + lo];
             }
-#ifdef RVSR_F3_PRIO   // (scratch variant, tools/build_variant.sh dcn3_kernels <name> -DRVSR_F3_PRIO: priority of the wave while it feeds the matrix core)
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(ah[mt], bh, acc[mt]);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) if (TERMS >= 2) acc[mt] = mfma_bf16(ah[mt], bl, acc[mt]);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) if (TERMS >= 3) acc[mt] = mfma_bf16(al[mt], bh, acc[mt]);
-#ifdef RVSR_F3_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef RVSR_F3_SGB    // (scratch variant: one MFMA per five vector instructions of the next tap's geometry instead of hipcc's clusters)
-#pragma unroll
-            for (int k = 0; k < 3 * MT; ++k) {
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 5, 0);
-            }
-#endif
-            if (chunk == 1) TSTAMP(40 + tap);
+            RVSR_STAMP(F3_TL && chunk == 1, F3_C1_TAP_END + tap);
         }
-        TSTAMP(5 + 6 * chunk);
+        RVSR_STAMP(F3_TL && chunk < 4, F3_CHUNK + 6 * chunk + 5);
         __syncthreads();
-        TSTAMP(6 + 6 * chunk);
+        RVSR_STAMP(F3_TL && chunk < 4, F3_CHUNK + 6 * chunk + 6);
     }
 
     if (oy >= d.Ho) return;
@@ -372,7 +345,7 @@ __global__ __launch_bounds__(512, (MT <= 2 && R == 3) ? 4 : 2) void dcn_fwd3_ker
             }
         }
     }
-    TSTAMP(30);
+    RVSR_STAMP(F3_TL, F3_EPILOGUE);
 }
 
 template <int MT, int R, int TERMS>

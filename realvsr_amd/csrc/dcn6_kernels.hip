@@ -41,15 +41,23 @@
 #include "dcn_tile.h"
 #include "dcn_plan.h"
 
-#ifdef RVSR_TIMELINE_DCN6   // s_memtime stamps of one wave of one workgroup (tools/dcn6_timeline.py); [0, 128): dcn_bwdin6, [128, 256): dcn_bwdw6
-__device__ unsigned long long rvsr_dbg_dcn6[256];
-extern "C" int rvsr_debug_read_dcn6(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rvsr_dbg_dcn6), sizeof(unsigned long long) * 256); }
-#define TS6(i) do { if (blockIdx.x == 77 && blockIdx.z == 1 && threadIdx.x == 192) rvsr_dbg_dcn6[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define TW6(i) do { if (blockIdx.x == 77 && threadIdx.x == 192) rvsr_dbg_dcn6[128 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TS6(i) do {} while (0)
-#define TW6(i) do {} while (0)
-#endif
+#include "timeline.h"
+
+// Timeline slots (timeline.h), read by tools/dcn6_timeline.py: lane 0 of wave 3 (thread 192) of one workgroup of each kernel
+#define BI6_TL (blockIdx.x == 77 && blockIdx.z == 1 && threadIdx.x == 192)
+#define BW6_TL (blockIdx.x == 77 && threadIdx.x == 192)
+enum Bwdin6Stamp {       // dcn_bwdin6_kernel, workgroup 77 of batch element 1
+    BI6_PROLOGUE = 0,    // gOut fragments, gOut^T emitted, window zeroed, chunk 0 requested
+    BI6_END = 9,
+    BI6_CHUNK = 10,      // + 8 * chunk (< 4) + {0: top, 1: x tile committed, 2: vmcnt(0), 3: barrier passed, 4: lane iterations done, 5: barrier passed,
+                         //                      6: next requests issued, 7: flush done}
+    BI6_C1_ITER = 50,    // + 4 * it + {0: start, 1: reads + math + atomics issued}, chunk 1, lane iteration it = 0..4
+    BI6_C1_MTILE = 90,   // + mt: chunk 1, MFMAs of M tile mt issued
+};
+enum Bwdw6Stamp {        // dcn_bwdw6_kernel, workgroup 77, the third tile of its stream
+    BW6_TILE = 128,      // + {0: top, 1: vmcnt(0): operands + x landed, 2: x committed + barrier, 3: next requests set up, 4: iterations done, 5: end barrier passed}
+    BW6_ITER = 138,      // + 4 * it + {0: start, 1: column values blended, 2: split + transposer issued}, lane iteration it = 0..4
+};
 
 // Lane iteration `it` (0..4) of lane half h works on tap (half 0, half 1): (0, 3), (1, 6), (4, 7), (2, 5), (8, none).  The two taps of an
 // iteration sit in DIFFERENT kernel rows: the halves' cells of one ds_add_u32 are then a window row (+-) apart and never the same cell.
@@ -171,10 +179,6 @@ __device__ __forceinline__ bf16x8 pack8_exact(const f32x16& d, int r0) {
 }
 
 
-#ifndef RVSR_ABL6
-#define RVSR_ABL6 0   // scratch ablation builds (tools/build_variant6.sh): bit mask of deleted ingredients, results wrong by construction:
-#endif                // 1 LDS atomics, 2 window flush, 4 corner reads, 8 col_grad MFMAs, 16 grad_offset / grad_mask stores, 32 requests of chunks 1.., 64 packed math
-
 struct DcnBwdIn6Params {
     DcnGeom d;
     TView g;            // grad_output view (Co, Ho, Wo), optional fused act'
@@ -225,18 +229,12 @@ __device__ __forceinline__ void bwd6_emit_agt(bf16x8* dst, int nmb32, const bf16
 
 // TERMS: terms of the bf16 product W^T * gOut (rvsr_common.h: gemm modes): 3 = hi*hi + hi*lo + lo*hi; 2 = without the weights' lo part;
 // 1 = hi*hi.  WPS: waves per SIMD the launch bounds promise (2 = one 8-wave workgroup per CU).
-#ifndef RVSR_BWDIN6_G2
-#define RVSR_BWDIN6_G2 1      // scratch builds: 0 = one grad_input window, flushed between the barriers (the round-5 structure)
-#endif
-#ifndef RVSR_BWDIN6_LBMUL
-#define RVSR_BWDIN6_LBMUL 1   // scratch builds: 2 = hold the kernel to the 128 registers that two 8-wave workgroups per CU need: 53-69 spilled
-#endif                        // registers, 6.1 instead of 4.4 ms per L1 launch (round 5 read the bound's second argument as workgroups per CU; it
-                              // is waves per SIMD -- the kernel has always run ONE workgroup per CU; profiles/r06_notes.md)
 // W2: two weight buffers in LDS (the DMA of chunk c + 1 is issued at the top of chunk c's iterations instead of after them).
 // G2: two grad_input windows in LDS: chunk c scatters into one while the other -- chunk c - 1's -- is flushed a few rows per lane iteration
 // of chunk c, inside the iterations' own stalls, instead of as a phase of its own between two barriers (round 6).
+// (the second argument of __launch_bounds__ is waves per SIMD, not workgroups per CU)
 template <int NK, int R, int TERMS, int WPS, bool W2, bool G2>
-__global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kernel(const DcnBwdIn6Params p, const bf16x8* __restrict__ wpack) {
+__global__ __launch_bounds__(512, WPS) void dcn_bwdin6_kernel(const DcnBwdIn6Params p, const bf16x8* __restrict__ wpack) {
     constexpr int TH = 8, NT = TH * 64;
     constexpr int TR = TH + 2 * R + 3, TC = 32 + 2 * R + 3, NPOS = TR * TC;
     constexpr int WBLK = 2 * (2 * NK) * 32;                        // vectors per (chunk, M tile): hi + lo
@@ -351,7 +349,7 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
     request_weights(0, wsb);
 #pragma unroll
     for (int k = 0; k < NXI; ++k) request_x_item(k, 0);
-    TS6(0);
+    RVSR_STAMP(BI6_TL, BI6_PROLOGUE);
 
     // ---- flush of window rows [r0, r1) of the chunk at channel cf0: wave w owns channel cf0 + w; one global atomic per touched cell inside the
     // image (the halos of neighbouring workgroups overlap), cell back to zero for its next use.  Round 6: a lane owns a window COLUMN and walks
@@ -362,7 +360,6 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
     const bool fl_col_ok = lane < TC && fl_xx >= 0 && fl_xx < d.W;
     const unsigned fl_col4 = 4u * (unsigned)(ty0 * d.W + fl_xx);   // (wraps for rows above the image: only used where the row test passed)
     auto flush_rows = [&](int* win, int cf0, float inv_s, int r0, int r1) {
-        if (RVSR_ABL6 & 2) return;
         const unsigned cpl = (unsigned)(cf0 + wave) * HW4;
         int* gc = win + wave * NPOS + lane;
         const bool ok = fl_col_ok && cf0 + wave < d.C;
@@ -394,7 +391,6 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
         for (int j = 0; j < FRB; ++j) v[j] = r0 + j < TR ? gc[(r0 + j) * TC] : 0;
     };
     auto flush_commit = [&](int* win, int cf0, float inv_s, int r0, const int (&v)[FRB]) {
-        if (RVSR_ABL6 & 2) return;
         const unsigned cpl = (unsigned)(cf0 + wave) * HW4;
         int* gc = win + wave * NPOS + lane;
         const bool ok = fl_col_ok && cf0 + wave < d.C;
@@ -414,20 +410,20 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
         const int g = c0 / d.cpg;
         int* const gwin = gwin0 + (G2 ? (chunk & 1) * 8 * NPOS : 0);
         int* const gwin_prev = gwin0 + (G2 ? ((chunk + 1) & 1) * 8 * NPOS : 0);
-        if (chunk < 4) TS6(10 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 0);
 #pragma unroll
         for (int k = 0; k < NXI; ++k) {
             const int it = tid + k * NT;
             if (it < 2 * NPOS) xt[it] = make_float4(xv[k][0], xv[k][1], xv[k][2], xv[k][3]);
         }
-        if (chunk < 4) TS6(11 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 1);
         if (!W2 || chunk == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the weight DMA has landed (W2: waited for below)
-        if (chunk < 4) TS6(12 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 2);
         __syncthreads();
-        if (chunk < 4) TS6(13 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 3);
         const int cn = chunk + 1 < nchunks ? chunk + 1 : chunk;   // (uniform) the chunk whose requests ride on this one's iterations; the last asks for itself
         bf16x8* const wcur = wsb + (W2 ? (chunk & 1) * 3 * WBLK : 0);
-        if (W2 && !(RVSR_ABL6 & 32)) request_weights(cn, wsb + ((chunk + 1) & 1) * 3 * WBLK);   // (the other buffer: read by chunk - 1, whose iterations are behind the barrier)
+        if (W2) request_weights(cn, wsb + ((chunk + 1) & 1) * 3 * WBLK);   // (the other buffer: read by chunk - 1, whose iterations are behind the barrier)
 
         // fixed-point scale of this chunk (file header): |contribution| * S <= 0.995 * 2^31 / 2304
         float S, invS;
@@ -449,7 +445,6 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
 #pragma unroll
             for (int ks = 0; ks < NK; ++ks) {
                 const bf16x8 ah = wb_hi[(2 * ks + hi) * 32 + lo];
-                if (RVSR_ABL6 & 8) { a[ks] += (float)ah[0] * (float)gh[ks][0] + (float)gl[ks][1]; a[ks + 8] += (float)ah[1]; continue; }
                 a = ks == 0 ? mfma_bf16_first(ah, gh[0]) : mfma_bf16(ah, gh[ks], a);
                 if (TERMS >= 2) a = mfma_bf16(ah, gl[ks], a);
                 if (TERMS >= 3) a = mfma_bf16(wb_lo[(2 * ks + hi) * 32 + lo], gh[ks], a);
@@ -472,12 +467,12 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
             } else {
                 acc = col_grad_tile(mt);
             }
-            if (chunk == 1) TS6(90 + mt);
+            RVSR_STAMP(BI6_TL && chunk == 1, BI6_C1_MTILE + mt);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int it = 2 * mt + s;
                 if (it >= 5) continue;   // (compile time)
-                if (chunk == 1) TS6(50 + 4 * it);
+                RVSR_STAMP(BI6_TL && chunk == 1, BI6_C1_ITER + 4 * it + 0);
                 int fv[FRB];
                 if (G2 && chunk > 0) flush_read(gwin_prev, it * FRB, fv);   // (uniform) the previous chunk's window: this iteration's share of rows
                 // weight fragments of this iteration's share of the NEXT M tile (k-steps ks0 .. ks0 + KH - 1)
@@ -502,11 +497,9 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                 // lanes without a pixel / a tap: zero offset, zero mask (their col_grad is 0 or belongs to zero weight rows)
                 const float dy = act_lane ? o_dy[it] : 0.f, dx = act_lane ? o_dx[it] : 0.f;
                 float m = o_m[it];
-                if (!(RVSR_ABL6 & 32)) {
-                    request_offsets(it, cn);   // (the registers just read: the next chunk's triple of this iteration)
+                request_offsets(it, cn);   // (the registers just read: the next chunk's triple of this iteration)
 #pragma unroll
-                    for (int k = it; k < NXI; k += 5) request_x_item(k, cn);   // (xv is free: committed to LDS at the top of this chunk)
-                }
+                for (int k = it; k < NXI; k += 5) request_x_item(k, cn);   // (xv is free: committed to LDS at the top of this chunk)
                 if (d.mask_logit) m = __builtin_amdgcn_rcpf(1.f + __expf(-m));
                 const float kyf = hi ? (float)(t1 / 3) : (float)(t0 / 3), kxf = hi ? (float)(t1 % 3) : (float)(t0 % 3);
                 // sample position in IMAGE coordinates exactly as the reference forms it (kernel.cu:594-616, 722-737)
@@ -527,13 +520,12 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                 float4 cr[2][4];   // both quads' corners up front: read inside the loop, the second quad's waited for the first quad's 16 atomics
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const float4* xq = xt + q * NPOS + ((RVSR_ABL6 & 4) ? 0 : pos0);
+                    const float4* xq = xt + q * NPOS + pos0;
                     cr[q][0] = xq[0]; cr[q][1] = xq[1]; cr[q][2] = xq[TC]; cr[q][3] = xq[TC + 1];
                 }
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    float4 a00 = cr[q][0], a01 = cr[q][1], a10 = cr[q][2], a11 = cr[q][3];
-                    if (RVSR_ABL6 & 4) { a00 = make_float4(ly, lx, hy, hx); a01 = make_float4(lx, ly, hx, hy); a10 = a01; a11 = a00; }
+                    const float4 a00 = cr[q][0], a01 = cr[q][1], a10 = cr[q][2], a11 = cr[q][3];
 #pragma unroll
                     for (int ph = 0; ph < 2; ++ph) {       // channel pairs (2 pr, 2 pr + 1), pr = 2 q + ph
                         const int pr = 2 * q + ph;
@@ -556,7 +548,6 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                         // (__float_as_uint, not __builtin_bit_cast(unsigned, u00.y): this hipcc compiles the bit_cast of a vector ELEMENT to element 0 -- /tmp test, r05_notes.md)
                         int* q0 = wq + (2 * pr) * NPOS;
                         int* q1 = q0 + NPOS;
-                        if (RVSR_ABL6 & 1) { gm2 = pk_fma(u00, u01, gm2); gy2 = pk_fma(u10, u11, gy2); continue; }
                         lds_add_i32_6(q0, (int)(__float_as_uint(u00.x) - 0x4B400000u));
                         lds_add_i32_6(q0 + 1, (int)(__float_as_uint(u01.x) - 0x4B400000u));
                         lds_add_i32_6(q0 + TC, (int)(__float_as_uint(u10.x) - 0x4B400000u));
@@ -565,7 +556,7 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                         lds_add_i32_6(q1 + 1, (int)(__float_as_uint(u01.y) - 0x4B400000u));
                         lds_add_i32_6(q1 + TC, (int)(__float_as_uint(u10.y) - 0x4B400000u));
                         lds_add_i32_6(q1 + TC + 1, (int)(__float_as_uint(u11.y) - 0x4B400000u));
-                        if (pre && pr < KH && ks0 + pr < NK && !(RVSR_ABL6 & 8)) {   // (compile time) one k-step of the next M tile
+                        if (pre && pr < KH && ks0 + pr < NK) {   // (compile time) one k-step of the next M tile
                             const int ks = ks0 + (pr < KH ? pr : 0);
                             acc_next = ks == 0 ? mfma_bf16_first(fh[pr < KH ? pr : 0], gh[0]) : mfma_bf16(fh[pr < KH ? pr : 0], gh[ks < NK ? ks : 0], acc_next);
                             if (TERMS >= 2) acc_next = mfma_bf16(fh[pr < KH ? pr : 0], gl[ks < NK ? ks : 0], acc_next);
@@ -575,7 +566,7 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                 }
                 float gm_s = gm2.x + gm2.y, gy_s = gy2.x + gy2.y, gx_s = gx2.x + gx2.y;
                 gm_s = in_tile ? gm_s : 0.f;
-                if (chunk == 1) TS6(51 + 4 * it);
+                RVSR_STAMP(BI6_TL && chunk == 1, BI6_C1_ITER + 4 * it + 1);
                 if (far) {   // ---- rare: the whole (pixel, tap) from global memory with the reference's rule set, plain arithmetic
                     const bool vy0 = yi >= 0, vy1 = yi + 1 <= d.H - 1, vx0 = xi >= 0, vx1 = xi + 1 <= d.W - 1;
                     const int cy0 = vy0 ? yi : 0, cy1 = vy1 ? yi + 1 : d.H - 1, cx0 = vx0 ? xi : 0, cx1 = vx1 ? xi + 1 : d.W - 1;
@@ -615,8 +606,7 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                     const unsigned tp = (unsigned)tap * pl4;
                     const unsigned so = act_lane ? pix4 + 2u * tp : 0xfffffffcu, sm = act_lane ? pix4 + tp : 0xfffffffcu;
                     const unsigned go_ = (unsigned)(g * 18) * pl4, gk = (unsigned)(g * 9) * pl4;
-                    if (RVSR_ABL6 & 16) { if (gy_s + gx_s + gm_s == 12345.678f) buf_store(goff_rs, so, go_, gy_s); }
-                    else if (first_of_group) {
+                    if (first_of_group) {
                         buf_store(goff_rs, so, go_, gy_s);
                         buf_store(goff_rs, so, go_ + pl4, gx_s);
                         buf_store(gmsk_rs, sm, gk, gm_s);
@@ -629,19 +619,19 @@ __global__ __launch_bounds__(512, WPS * RVSR_BWDIN6_LBMUL) void dcn_bwdin6_kerne
                 if (G2 && chunk > 0) flush_commit(gwin_prev, c0 - 8, invS_prev, it * FRB, fv);
             }
         }
-        if (chunk < 4) TS6(14 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 4);
         __syncthreads();
-        if (chunk < 4) TS6(15 + 8 * chunk);
-        if (!W2 && !(RVSR_ABL6 & 32)) request_weights(cn, wsb);   // (one weight buffer: free now; in flight while the window is flushed, waited for at the top)
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 5);
+        if (!W2) request_weights(cn, wsb);   // (one weight buffer: free now; in flight while the window is flushed, waited for at the top)
         if (W2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA issued at the top of the iterations (hipcc does not count it); the loads behind it are a barrier old
-        if (chunk < 4) TS6(16 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 6);
         if (!G2) flush_rows(gwin, c0, invS, 0, TR);   // (G2: during the next chunk's iterations / after the loop)
         invS_prev = invS;
         // (the barrier after the next commit orders this flush before the next chunk's atomics)
-        if (chunk < 4) TS6(17 + 8 * chunk);
+        RVSR_STAMP(BI6_TL && chunk < 4, BI6_CHUNK + 8 * chunk + 7);
     }
     if (G2) flush_rows(gwin0 + ((nchunks - 1) & 1) * 8 * NPOS, (nchunks - 1) * 8, invS_prev, 0, TR);   // (behind the last chunk's barrier)
-    TS6(9);
+    RVSR_STAMP(BI6_TL, BI6_END);
 }
 
 // Sampled statistic behind the halo selection of both DCN directions: every 16th row of every offset plane;
@@ -699,7 +689,7 @@ static int launch_bwdin6(const DcnBwdIn6Params& p, int nt, const bf16x8* wpack, 
     constexpr size_t gbytes = (size_t)NPOS * 8 * 4;
     // (NK = 8, the nf128 packs: the 48 KB weight block first -- measured at R = 5, where only one of the two fits: 4.01 against 4.21 ms)
     constexpr bool W2_FIRST = NK >= 8;
-    constexpr bool G2 = RVSR_BWDIN6_G2 && lds1 + gbytes + (W2_FIRST && lds1 + wbytes <= 160 * 1024 ? wbytes : 0) <= 160 * 1024;
+    constexpr bool G2 = lds1 + gbytes + (W2_FIRST && lds1 + wbytes <= 160 * 1024 ? wbytes : 0) <= 160 * 1024;
     constexpr bool W2 = lds1 + (G2 ? gbytes : 0) + wbytes <= 160 * 1024;
     constexpr size_t lds = lds1 + (G2 ? gbytes : 0) + (W2 ? wbytes : 0);
     constexpr int WPS = 2;   // waves per SIMD the launch bounds name: ONE 8-wave workgroup per CU (~220 registers per lane)
@@ -788,9 +778,6 @@ int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const DcnBwdPlan& q, const float* w
 // Three things this kernel taught (profiles/r05_notes.md): the untied first MFMA of an accumulator must keep its operands alive
 // (bf16x3.h: mfma_bf16_first); no rolled loop inside a divergent branch (the far path is unrolled: 32 loads in flight); two workgroups of four
 // waves per CU gave run-to-run different weight gradients for a reason that was not found -- one workgroup per CU does not.
-#ifndef RVSR_ABLW6
-#define RVSR_ABLW6 0   // scratch ablation builds (tools/build_variant.sh), results wrong by construction: 1 no operand LDS-DMA after the first tile, 2 no x
-#endif                 // loads, 4 no offset / mask loads, 8 no weight-gradient MFMAs, 16 no corner reads
 struct DcnBwdW6Params {
     DcnGeom d;
     const bf16x8* agt;  // gOut x act' as A operands, written by dcn_bwdin6 (bwd6_emit_agt): [b][row][x tile][mb32][ks][hi, lo][lane]
@@ -914,18 +901,18 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
         const float by = (float)(oy - d.pad), bx = (float)(ox - d.pad);
         const int set = (t - t_begin) & 1;
         bf16x8* my_ag = agt + ((set * TH + wave) * 8) * 64 + lane;   // vector (mb, ks, part) at [(mb * 4 + ks * 2 + part) * 64]
-        const bool tl = t == t_begin + 2;
-        if (tl) TW6(0);
+        const bool tl = t == t_begin + 2;   // (timeline.h: the tile that is stamped)
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 0);
         // ---- this tile's operand vectors have landed (requested a tile ago; hipcc does not count LDS-DMA); commit the x tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tl) TW6(1);
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 1);
 #pragma unroll
         for (int k = 0; k < NXI; ++k) {
             const int it = tid + k * NT;
             if (it < 2 * NPOS) xt[it] = make_float4(xv[k][0], xv[k][1], xv[k][2], xv[k][3]);
         }
         __syncthreads();
-        if (tl) TW6(2);
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 2);
         // ---- the next tile's requests (the last tile asks for itself again: unconditional loads keep hipcc's s_waitcnt bookkeeping simple).
         // They are issued a slice per lane iteration below, not as one burst here: 39 vector-memory instructions per wave in a row took 3.6 K of a
         // tile's 14 K cycles to ISSUE (the texture path takes ~100 cycles per instruction with eight waves asking at once) and the first iteration
@@ -935,20 +922,20 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
         const __amdgpu_buffer_rsrc_t off_rs_n = buf_view(d.offset + (size_t)bn * d.off_bs), msk_rs_n = buf_view(d.mask + (size_t)bn * d.mask_bs);
         const unsigned pv_n = pixel_offset(y0n, x0n);
 
-        if (tl) TW6(3);
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 3);
         f32x16 dt_h, dt_l;   // column values of two lane iterations, transposed: D[i = pixel][j = 16 (it & 1) + 8 h + ch]
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
             const int t0 = bwd6_tap(it, 0), t1 = it < 4 ? bwd6_tap(it, 1) : 0;
             const bool has_tap = it < 4 || hi == 0;
             const bool act_lane = px_ok && has_tap;
-            if (tl) TW6(10 + 4 * it);
+            RVSR_STAMP(BW6_TL && tl, BW6_ITER + 4 * it + 0);
             const float dy = act_lane ? o_dy[it] : 0.f, dx = act_lane ? o_dx[it] : 0.f;
             float m = o_m[it];
-            if (!(RVSR_ABLW6 & 4)) request_offsets(it, off_rs_n, msk_rs_n, pv_n);   // (the registers just read: the next tile's triple of this iteration)
-            if (it < 4 && !(RVSR_ABLW6 & 1)) fetch_ag(bn, y0n, x0n, set ^ 1, 2 * it, 2 * it + 2);
+            request_offsets(it, off_rs_n, msk_rs_n, pv_n);   // (the registers just read: the next tile's triple of this iteration)
+            if (it < 4) fetch_ag(bn, y0n, x0n, set ^ 1, 2 * it, 2 * it + 2);
 #pragma unroll
-            for (int k = it; k < NXI; k += 5) if (!(RVSR_ABLW6 & 2)) request_x_item(k, bn, y0n, x0n);   // (xv is free: committed to LDS above)
+            for (int k = it; k < NXI; k += 5) request_x_item(k, bn, y0n, x0n);   // (xv is free: committed to LDS above)
             if (d.mask_logit) m = __builtin_amdgcn_rcpf(1.f + __expf(-m));
             const float kyf = hi ? (float)(t1 / 3) : (float)(t0 / 3), kxf = hi ? (float)(t1 % 3) : (float)(t0 % 3);
             // sample position in IMAGE coordinates exactly as the reference forms it (kernel.cu:594-616)
@@ -970,8 +957,7 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const float4* xq = xt + q * NPOS + pos0;
-                float4 a00 = xq[0], a01 = xq[1], a10 = xq[TC], a11 = xq[TC + 1];
-                if (RVSR_ABLW6 & 16) { a00 = make_float4(ly, lx, ml, ly); a01 = make_float4(lx, ly, ml, lx); a10 = a01; a11 = a00; }
+                const float4 a00 = xq[0], a01 = xq[1], a10 = xq[TC], a11 = xq[TC + 1];
 #pragma unroll
                 for (int ph = 0; ph < 2; ++ph) {
                     const f32x2 c00 = ph ? f32x2{a00.z, a00.w} : f32x2{a00.x, a00.y};
@@ -1003,7 +989,7 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
 #pragma unroll
                 for (int e = 0; e < 8; ++e) colv[e] = u00 * q00[e] + u01 * q01[e] + u10 * q10[e] + u11 * q11[e];
             }
-            if (tl) TW6(11 + 4 * it);
+            RVSR_STAMP(BW6_TL && tl, BW6_ITER + 4 * it + 1);
             // (spare slot of iteration 4, half 1: the ones column of the bias gradient)
             if (it == 4) colv[0] = hi ? (px_ok ? 1.f : 0.f) : colv[0];
             bf16x8 ch_, cl_;
@@ -1015,7 +1001,7 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
                 dt_h = mfma_bf16(ch_, sel_o, dt_h);
                 if (TERMS >= 2) dt_l = mfma_bf16(cl_, sel_o, dt_l);
             }
-            if (tl) TW6(12 + 4 * it);
+            RVSR_STAMP(BW6_TL && tl, BW6_ITER + 4 * it + 2);
             if ((it & 1) || it == 4) {   // ---- n-block nb = it / 2 complete: gw_acc[mb][nb] += gOut^T[mb] x col, K = this row's 32 pixels
                 const int nb = it >> 1;
 #pragma unroll
@@ -1026,7 +1012,6 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb) {
                         const bf16x8 ah = my_ag[(mb * 4 + ks * 2) * 64];
-                        if (RVSR_ABLW6 & 8) { gw_acc[mb][nb][ks] += (float)ah[0] * (float)bh[1] + (float)bl[2]; continue; }
                         gw_acc[mb][nb] = mfma_bf16(ah, bh, gw_acc[mb][nb]);
                         if (TERMS >= 2) gw_acc[mb][nb] = mfma_bf16(ah, bl, gw_acc[mb][nb]);
                         if (TERMS >= 3) gw_acc[mb][nb] = mfma_bf16(my_ag[(mb * 4 + ks * 2 + 1) * 64], bh, gw_acc[mb][nb]);
@@ -1034,9 +1019,9 @@ __global__ __launch_bounds__(TH * 64, 2) void dcn_bwdw6_kernel(const DcnBwdW6Par
                 }
             }
         }
-        if (tl) TW6(4);
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 4);
         __syncthreads();   // (every wave is done with the x tile)
-        if (tl) TW6(5);
+        RVSR_STAMP(BW6_TL && tl, BW6_TILE + 5);
     }
 
     // ---- partial of this (stream, unit): sum of the waves (rows), fixed order, through LDS.  The last tile asked for itself again: that

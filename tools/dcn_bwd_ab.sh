@@ -1,6 +1,7 @@
 #!/bin/bash
-# DCN backward, one gpurun call: parity of the DCN suites, per-kernel A/B of library variants, timeline
+# DCN backward in one go: parity of the DCN suites, per-kernel A/B of library variants, timeline
 #   tools/dcn_bwd_ab.sh [variant specs for tools/ab_kernels.sh ...]
+# (the timeline runs when its variant exists: tools/build_variant.sh tl6 dcn6_kernels.hip -DRVSR_TIMELINE)
 mkdir -p gpurun_out
 L=gpurun_out/dcn_bwd_ab.log
 : > $L
