@@ -39,6 +39,8 @@ enum Fwd5Stamp {
 enum Wgrad2Stamp {
     WG2_T3_KSTEP = 120,     // + 10 * wave + {0..7: start of k-step, 8: k-steps done}, tile 3
     WG2_TILE = 200,         // + 4 * ti + {0: top, 1: committed to LDS, 2: opening barrier passed, 3: MFMA phase (+ next tile's loads) done}, thread 0
+    WG2_LOOP_END = 230,     // thread 0, behind the tile loop: the partial sums start
+    WG2_KERNEL_END = 231,   // thread 0, behind the partial sums and the bias partials
 };
 
 // ------------------------------------------------------------------------------------------
@@ -143,6 +145,86 @@ __device__ __forceinline__ void conv2_epilogue_v4(f32x16 (&acc)[MT][2], const Co
                 v.z = v.z > 0.f ? v.z : v.z * neg; v.w = v.w > 0.f ? v.w : v.w * neg;
                 if (MODE == 1) { v.x += resv[rg].x; v.y += resv[rg].y; v.z += resv[rg].z; v.w += resv[rg].w; }
                 buf_store4(out_rs, off[rg] + (unsigned)(o0 + m * 32 + 8 * rg) * HW4, 0u, v);
+            }
+        }
+    }
+}
+
+// conv2_epilogue_v4 for the split output (MODE 2) when the launcher grants it (p.vec4, rvsr_launch_conv_fwd2: Co1 % 8 == 0, Wout % 4 == 0, 16-byte aligned outputs, spans < 2 GB): the same body, with the buffer view and
+// the channel base chosen per group of eight channels -- Co1 % 8 == 0, so a group lies entirely in out1 (below Co1) or in out2.  (A function
+// of its own, not a third MODE of conv2_epilogue_v4: conv_fwd2_kernel shares that one, and its code is not to move with this path.)
+template <int MT>
+__device__ __forceinline__ void conv2_epilogue_split4(f32x16 (&acc)[MT][2], const ConvFwdParams& p, const float* bias_s, int b,
+                                                      int o0, int row0, int x0, int lo, int hi) {
+    const float neg = p.act == 0 ? 1.f : (p.act == 1 ? 0.f : p.slope);
+    const int j = lo & 3, col4 = x0 + (lo & ~3);
+    const bool col_ok = col4 < p.Wout;
+    const unsigned HW = (unsigned)(p.Hout * p.Wout), HW4 = 4u * HW;
+    const __amdgpu_buffer_rsrc_t out1_rs = buf_view_2g(p.out1 + (size_t)b * p.Co1 * HW);
+    const __amdgpu_buffer_rsrc_t out2_rs = buf_view_2g(p.out2 + (size_t)b * (p.Co - p.Co1) * HW);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int row = row0 + n;
+        if (row >= p.Hout) continue;  // wave-uniform
+        const unsigned lane_off = 4u * ((unsigned)(4 * hi + j) * HW + (unsigned)row * p.Wout + col4);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int ob = o0 + m * 32 + 8 * rg;   // (uniform) first channel of the group of 8
+                const bool first = ob < p.Co1;         // (uniform)
+                const unsigned off = (col_ok && ob + 4 * hi + j < p.Co ? lane_off : 0x80000000u) + (unsigned)(first ? ob : ob - p.Co1) * HW4;
+                float r0 = acc[m][n][4 * rg + 0], r1 = acc[m][n][4 * rg + 1], r2 = acc[m][n][4 * rg + 2], r3 = acc[m][n][4 * rg + 3];
+                quad_transpose4(r0, r1, r2, r3, lo);
+                const float bb = bias_s[m * 32 + 8 * rg + 4 * hi + j];
+                float4 v = make_float4(r0 + bb, r1 + bb, r2 + bb, r3 + bb);
+                v.x = v.x > 0.f ? v.x : v.x * neg; v.y = v.y > 0.f ? v.y : v.y * neg;
+                v.z = v.z > 0.f ? v.z : v.z * neg; v.w = v.w > 0.f ? v.w : v.w * neg;
+                // (two store sites with one fixed descriptor each, not one store with a selected descriptor: see the note on soffset above)
+                if (first) buf_store4(out1_rs, off, 0u, v);
+                else buf_store4(out2_rs, off, 0u, v);
+            }
+        }
+    }
+}
+
+// 8-byte-store epilogue of the pixel-shuffle case (MODE 3) when the output base is 8-byte aligned and one batch element of the output
+// spans < 2 GB (p.vec4 with p.ps, rvsr_launch_conv_fwd2).  Registers 4 rg .. 4 rg + 3 of a lane are the four channels of ONE shuffle
+// group (channels ob + 4 hi + 0..3, ob % 8 == 0) at the lane's pixel, i.e. the 2 x 2 output block at (2 row, 2 col) of output plane
+// (ob + 4 hi) >> 2: {r0, r1} goes to output row 2 row, {r2, r3} to row 2 row + 1, no transpose, and the 32 lanes of a half write one run
+// of 256 bytes per store.  Addressing as in conv2_epilogue_v4: one 32-bit lane offset per row + the group's offset, added on the vector side.
+__device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t rs, unsigned lane_bytes, float a, float b) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 w = {__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b)};
+    __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)lane_bytes, 0, 0);
+}
+template <int MT>
+__device__ __forceinline__ void conv2_epilogue_ps2(f32x16 (&acc)[MT][2], const ConvFwdParams& p, const float* bias_s, int b,
+                                                   int o0, int row0, int col, int hi) {
+    const float neg = p.act == 0 ? 1.f : (p.act == 1 ? 0.f : p.slope);
+    const bool col_ok = col < p.Wout;
+    const unsigned HW = (unsigned)(p.Hout * p.Wout);
+    const unsigned row8 = 8u * (unsigned)p.Wout, pl16 = 16u * HW;   // bytes of one output row (2 Wout floats) / output plane (4 HW floats)
+    const __amdgpu_buffer_rsrc_t out_rs = buf_view_2g(p.out1 + (size_t)b * p.Co * HW);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int row = row0 + n;
+        if (row >= p.Hout) continue;  // wave-uniform
+        const unsigned lane_off = (unsigned)hi * pl16 + (unsigned)(2 * row) * row8 + 8u * (unsigned)col;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int ob = o0 + m * 32 + 8 * rg;   // (uniform) first channel of the group of 8 = two shuffle groups, one per lane half
+                const unsigned off = (col_ok && ob + 4 * hi < p.Co ? lane_off : 0x80000000u) + (unsigned)(ob >> 2) * pl16;   // (Co % 4 == 0)
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float t = acc[m][n][4 * rg + e] + bias_s[m * 32 + 8 * rg + 4 * hi + e];
+                    v[e] = t > 0.f ? t : t * neg;
+                }
+                buf_store2(out_rs, off, v[0], v[1]);
+                buf_store2(out_rs, off + row8, v[2], v[3]);
             }
         }
     }
@@ -851,6 +933,11 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
         const bf16x8* ws_lo = ws_hi + WVEC;
         constexpr bool pub = true;    // publish stage q+1 into the other buffer during this stage (garbage after the last stage)
         bf16x8 ah[2][MT], al[2][MT], bh[2][2], bl[2][2];
+        // Zero-insert view (VEC == 3): only even virtual input rows hold data.  The tile origin y0 is a multiple of 16 and a wave's rows are
+        // y0 + 2 wave + n, so (N tile n, tap row dy) reads the virtual row y0 + 2 wave + n + dy - 1: even exactly when n + dy is odd.  The
+        // other pairs (n = 0: dy 0, 2; n = 1: dy 1) multiply staged zeros: neither their B fragments are read nor their MFMAs issued,
+        // 9 of the 18 (n, tap) pairs of a chunk.  (The sums lose additions of exact zeros only.)
+        auto live = [](int n, int tap) { return VEC != 3 || ((n + tap / KS) & 1) != 0; };
         auto fetch = [&](int tap, int slot) {
             const int dy = tap / KS, dx = tap % KS;
 #pragma unroll
@@ -860,6 +947,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
             }
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
+                if (!live(n, tap)) continue;
                 const int idx = WIDE ? (hi * IH + wave + dy) * IW + lo + 32 * n + dx : (hi * IH + wave * 2 + n + dy) * IW + lo + dx;
                 bh[slot][n] = xs_hi[idx];
                 if (NT >= 2) bl[slot][n] = xs_lo[idx];
@@ -910,18 +998,21 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) acc[m][n] = mfma_bf16(ah[sl][m], bh[sl][n], acc[m][n]);
+                for (int n = 0; n < 2; ++n)
+                    if (live(n, tap)) acc[m][n] = mfma_bf16(ah[sl][m], bh[sl][n], acc[m][n]);
             if (NT >= 2) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
-                    for (int n = 0; n < 2; ++n) acc[m][n] = mfma_bf16(ah[sl][m], bl[sl][n], acc[m][n]);
+                    for (int n = 0; n < 2; ++n)
+                        if (live(n, tap)) acc[m][n] = mfma_bf16(ah[sl][m], bl[sl][n], acc[m][n]);
             }
             if (NT >= 3) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
-                    for (int n = 0; n < 2; ++n) acc[m][n] = mfma_bf16(al[sl][m], bh[sl][n], acc[m][n]);
+                    for (int n = 0; n < 2; ++n)
+                        if (live(n, tap)) acc[m][n] = mfma_bf16(al[sl][m], bh[sl][n], acc[m][n]);
             }
             }
             // ---- this wave's own staging work, a slice per tap, in the shadow of the MFMAs above (a wave's own
@@ -953,11 +1044,13 @@ __global__ __launch_bounds__(512, 2) void conv_fwd5_kernel(const ConvFwdParams p
                 else if (p.res_period > 0) conv2_epilogue_wide<MT, 5>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else if (p.res != nullptr) conv2_epilogue_wide<MT, 1>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
                 else conv2_epilogue_wide<MT, 0>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave, cur.x0, lo, hi);
-            } else if (p.ps)
-                conv2_epilogue<MT, 3>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
-            else if (p.out2 != nullptr)
-                conv2_epilogue<MT, 2>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
-            else if (p.res != nullptr) {
+            } else if (p.ps) {
+                if (p.vec4) conv2_epilogue_ps2<MT>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
+                else conv2_epilogue<MT, 3>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
+            } else if (p.out2 != nullptr) {
+                if (p.vec4) conv2_epilogue_split4<MT>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0, lo, hi);
+                else conv2_epilogue<MT, 2>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
+            } else if (p.res != nullptr) {
                 if (p.vec4) conv2_epilogue_v4<MT, 1>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0, lo, hi);
                 else conv2_epilogue<MT, 1>(acc, p, bias_s, cur.b, cur.mb * MP, cur.y0 + wave * 2, cur.x0 + lo, hi);
             } else {
@@ -1047,6 +1140,12 @@ int rvsr_launch_conv_fwd2(ConvFwdParams p, const ConvFwdPlan& q, int ksize, int 
     }
     p.wpack = workspace;
     p.vec4 = q.vec4;
+    // conv_fwd5's vector-store epilogues of the two output modes the plan's vec4 leaves out (no new parameter field: one more field, even in the
+    // struct's tail padding, moves the code of every conv_fwd2_kernel instantiation)
+    if (five && p.ps) p.vec4 = ((uintptr_t)p.out1 & 7) == 0 && conv_span_ok(p.Hout, p.Wout, p.Co);
+    if (five && !p.ps && p.out2 != nullptr)
+        p.vec4 = p.Co1 % 8 == 0 && p.Wout % 4 == 0 && conv_al16(p.out1, p.out2) && conv_span_ok(p.Hout, p.Wout, p.Co1) &&
+                 conv_span_ok(p.Hout, p.Wout, p.Co - p.Co1);
     return rvsr_conv_launch(five ? "conv_fwd5" : "conv_fwd2", k, dim3(q.gx), five ? 512 : 256, q.lds, st, p);
 }
 
@@ -1392,7 +1491,42 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
         __syncthreads();
     }
 
-    if (m_live) {
+    RVSR_STAMP(WG2_TL_THREAD0, WG2_LOOP_END);
+    // Partial sums.  Straight from the accumulators a store instruction puts 64 separate 4-byte values 36 bytes apart, 64-80 such
+    // instructions per wave, and every workgroup of the launch reaches this point at about the same time.  The operand tiles are dead by
+    // now: the waves of one M tile at a time lay their accumulators out in LDS as [o (32)][c (64)][tap (9)] floats (73,728 bytes), which
+    // is the order of `part` -- row o is ONE run of 576 floats at part + ((blockIdx.x * Co + o) * Ctot + c0) * 9 -- and all 512 threads
+    // copy the rows out with 16-byte stores.  Needs Ctot % 4 == 0 (a row's valid part, 9 * min(64, Ctot - c0) floats, and every row start are
+    // then whole float4s) and a 16-byte aligned workspace; otherwise the element loop below runs.  Same values at the same addresses.
+    const bool vec_tail = (Ctot & 3) == 0 && (reinterpret_cast<uintptr_t>(p.part) & 15) == 0;   // (uniform)
+    if (vec_tail) {
+        float* stage = reinterpret_cast<float*>(smem_raw);
+        const int ntap = second ? 4 : 5, tap0 = second ? 5 : 0;
+        const int nrem = Ctot - c0, nf4 = ((nrem < 64 ? nrem : 64) * 9) >> 2;   // float4s of a row that exist
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            if (m == mt && m_live) {
+                float* dst = stage + ((4 * hi) * 64 + chalf * 32 + lo) * 9 + tap0;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    if (i >= ntap) continue;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2)) * 576 + i] = acc[i][r];   // row drow(r, hi)
+                }
+            }
+            __syncthreads();
+            const int obase = mb * 64 + mt * 32;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {   // 32 rows x 144 float4 = 9 per thread
+                const int v = tid + i * WG2_THREADS;
+                const int ol = v / 144, q = v - ol * 144;
+                if (obase + ol < p.Co && q < nf4)
+                    *reinterpret_cast<float4*>(p.part + (((size_t)blockIdx.x * p.Co + obase + ol) * Ctot + c0) * 9 + 4 * q) =
+                        *reinterpret_cast<const float4*>(stage + ol * 576 + 4 * q);
+            }
+            if (mt == 0) __syncthreads();
+        }
+    } else if (m_live) {
         const int c = c0 + chalf * 32 + lo;
         const int ntap = second ? 4 : 5, tap0 = second ? 5 : 0;
 #pragma unroll
@@ -1423,6 +1557,7 @@ __global__ __launch_bounds__(WG2_THREADS, 2) void conv_wgrad2_kernel(const ConvW
             if (o < p.Co) p.bpart[(size_t)blockIdx.x * p.Co + o] = bsum[tid];
         }
     }
+    RVSR_STAMP(WG2_TL_THREAD0, WG2_KERNEL_END);
 }
 
 typedef void (*ConvWgradKernel)(const ConvWgradParams);

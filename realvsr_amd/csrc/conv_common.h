@@ -8,7 +8,8 @@ struct ConvFwdParams {
     const float* w;
     const void* wpack;  // bf16x3 path: packed weights (conv2_kernels.hip)
     int swz;            // XCD-aware workgroup remap on/off
-    int vec4;           // 16-byte-store epilogue usable (Wout % 4 == 0, aligned pointers)
+    int vec4;           // the vector-store epilogue of this call's output mode is usable (rvsr_launch_conv_fwd2): plain / residual: 16-byte stores, the
+                        // plan's vec4 (Wout % 4 == 0, aligned pointers); conv_fwd5 also: split output, 16-byte stores; pixel shuffle, 8-byte stores
     const float* bias;
     const float* res;
     float* out1;
