@@ -1,6 +1,6 @@
 """Parity spot-check run in a SUBPROCESS by tests/test_gpu_switches.py with one developer switch set (the switches are read once
-per process): a fused DCN pack forward + backward against the CPU oracle at three offset scales, and a 3x3 / 1x1 / stride-2
-conv block against float64 torch.  Exit code 0 = all within the op-level bf16x3 tolerance (1e-4 of the tensor's max)."""
+per process): the modulated DCN operator forward + backward against the CPU oracle at three offset scales, the fused DCN pack node
+with a LeakyReLU against its float64 reference (tests/dcn_pack_reference.py), and a 3x3 / 1x1 / stride-2 conv block against float64 torch.  Exit code 0 = all within the op-level bf16x3 tolerance (1e-4 of the tensor's max)."""
 import os
 import sys
 
@@ -32,6 +32,22 @@ def main():
         errs = [rel_err(a.grad.cpu(), b.grad) for a, b in zip(got, ref)]
         errs.append(rel_err(out.detach().cpu(), oracle_dcn(*[x.detach() for x in ref], 1, 1, 1, 1, 8)))
         print('dcn', C, Co, H, W, ostd, ' '.join('%.1e' % e for e in errs))
+        worst = max(worst, max(errs))
+    # the node the network calls: RF.dcn_pack on the raw conv_offset_mask output with a LeakyReLU (the epilogue, act' in the gradient
+    # kernels -- with RVSR_DCN_BWD=64: dcn_bwdin6 without hand-off + dcn_bwdw4 with act'), against tests/dcn_pack_reference.py
+    import dcn_pack_reference as DR
+    for C, Co, H, W, ostd in ((64, 64, 24, 40, 4.0),):
+        g = torch.Generator().manual_seed(C + H + 1)
+        om = torch.randn(1, 216, H, W, generator=g)
+        om[:, :144] *= ostd
+        t = [torch.randn(1, C, H, W, generator=g), om, torch.randn(Co, C, 3, 3, generator=g) / (3 * C ** 0.5), torch.randn(Co, generator=g)]
+        r = DR.reference(*t, 1, 1, 1, 8, 'lrelu', 0.1, torch.randn(1, Co, H, W, generator=g))
+        assert r['share'] <= DR.KINK_SHARE_MAX, r['share']
+        got = [x.to(d).requires_grad_(True) for x in t]
+        out = RF.dcn_pack(*got, 1, 1, 1, 8, act=RF.ACT_LRELU, slope=0.1)
+        out.backward(r['gout'].to(d))
+        errs = [rel_err(a.grad.cpu(), b) for a, b in zip(got, (r['gx'], r['gom'], r['gw'], r['gb']))] + [rel_err(out.detach().cpu(), r['out'])]
+        print('dcn_pack lrelu', C, Co, H, W, ostd, ' '.join('%.1e' % e for e in errs))
         worst = max(worst, max(errs))
     # (the 24 x 128 frame takes the 8 x 64 tile of conv_fwd5, the 36 x 72 ones its 16 x 32 tile)
     for k, s, Ci, Co, Hc, Wc in ((3, 1, 64, 64, 36, 72), (3, 1, 64, 64, 24, 128), (3, 1, 128, 216, 36, 72), (1, 1, 64, 64, 36, 72), (3, 2, 64, 64, 36, 72)):

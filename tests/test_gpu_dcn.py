@@ -51,19 +51,22 @@ def test_fixture_dcn_op(gemm_mode):
 
 SHAPES = [
     # B, C, Co, dg, H, W, stride, pad, dil, offset_std, bias
-    (2, 64, 64, 8, 20, 36, 1, 1, 1, 2.0, True),     # EDVR L1-like, cpg 8
+    (2, 64, 64, 8, 20, 36, 1, 1, 1, 2.0, True),     # EDVR L1-like, cpg 8 (the 5 px window)
     (1, 128, 128, 8, 12, 40, 1, 1, 1, 1.0, True),   # nf128, cpg 16 (two chunks per group)
     (2, 16, 12, 4, 7, 9, 1, 1, 1, 3.0, True),       # cpg 4 (two groups per chunk), ragged tile
-    (1, 64, 64, 8, 45, 80, 1, 1, 1, 10.0, True),    # large motion, L3 size of 180x320
+    (1, 64, 64, 8, 45, 80, 1, 1, 1, 10.0, True),    # large motion, L3 size of 180x320 (the 12 px window)
     (1, 32, 40, 4, 9, 33, 1, 1, 1, 1.0, False),     # no bias, Co not multiple of 32
     (1, 16, 16, 2, 11, 13, 2, 1, 1, 1.0, True),     # stride 2
     (1, 16, 16, 2, 11, 13, 1, 2, 2, 1.0, True),     # dilation 2
     (1, 8, 72, 1, 6, 34, 1, 1, 1, 1.0, True),       # Co > 64 (MT=4 path), dg 1
     (1, 64, 80, 8, 10, 36, 1, 1, 1, 0.5, True),     # backward in two output-channel passes (64 + 16)
-    # the backward picks its window halo on the device from the offsets (dcn6_kernels.hip, rvsr_launch_dcn_bwdin6: 2 / 4 / 5 / 8 / 12 px):
-    (1, 64, 64, 8, 24, 40, 1, 1, 1, 3.0, True),     # 40 % of the components beyond 2.5 px: the 5 px window
-    (1, 64, 64, 8, 24, 40, 1, 1, 1, 6.0, True),     # 68 %: the 12 px window
-    (1, 128, 128, 8, 17, 40, 1, 1, 1, 8.0, True),   # Co > 64 (NK = 8): windows 2 / 4 / 5 / 8 px only
+    # the backward picks its window halo on the device from the offsets (dcn6_kernels.hip, rvsr_launch_dcn_bwdin6: 2 / 4 / 5 / 8 / 12 px;
+    # the windows below are what the host rule of tests/dcn_ledger.py computes from these offsets: 2 % of the sampled components is 231).
+    # The forward of this operator has neither probe nor hint: its tile is 3 px whatever the offsets (tests/test_gpu_dcn_pack_node.py
+    # runs the 7 and 11 px tiles).
+    (1, 64, 64, 8, 24, 40, 1, 1, 1, 3.0, True),     # 7 % of the components beyond 5.5 px, 0.5 % beyond 8.5 px: the 8 px window
+    (1, 64, 64, 8, 24, 40, 1, 1, 1, 6.0, True),     # 16 % beyond 8.5 px: the 12 px window
+    (1, 128, 128, 8, 17, 40, 1, 1, 1, 8.0, True),   # Co > 64 (NK = 8): windows 2 / 4 / 5 / 8 px only; 28 % beyond 8.5 px: the 8 px window
 ]
 
 
@@ -83,8 +86,8 @@ def test_random_shapes_vs_oracle(shape, gemm_mode):
 
 
 def _random_shapes(n, seed):
-    """Seeded sweep: channel / group counts on both sides of the 8-channel octet, ragged tiles, every offset regime of the
-    device-side backward selection (private windows, 3 px and 5 px halo, global fallback)."""
+    """Seeded sweep: channel / group counts on both sides of the 8-channel octet, ragged tiles, offset scales from 0.3 to 9 px (which
+    windows of the device-side backward selection they reach at which NK: the tables of tests/test_dcn_ledger_host.py)."""
     import random
     rnd = random.Random(seed)
     out = []
@@ -128,7 +131,7 @@ COMPOSITION_CASES = [
     # B, C, Co, dg, H, W, seed
     (2, 64, 64, 8, 20, 36, 21),     # cpg 8: dcn_fwd3 / dcn_bwdin6 / dcn_bwdw6
     (1, 128, 64, 8, 12, 40, 22),    # cpg 16 (two chunks per deformable group)
-    (2, 16, 12, 4, 7, 9, 23),       # cpg 4 (two groups per chunk): the fifth-generation backward
+    (2, 16, 12, 4, 7, 9, 23),       # cpg 4 (two groups per chunk): the three first-generation kernels
     (1, 8, 6, 1, 9, 33, 24),        # one deformable group
 ]
 
