@@ -640,6 +640,41 @@ int rvsr_avgpool2_backward(const float* gout, float* gin, size_t planes, int H, 
 int rvsr_upsample2_ac_forward(const float* in, float* out, size_t planes, int H, int W, float scale, void* stream);
 int rvsr_upsample2_ac_backward(const float* gout, float* gin, size_t planes, int H, int W, float scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 11. Validation metrics (codes/train.py:274-320, codes/test_RealVSR_wi_GT.py:134-168, utils/util.py:283-334)
+ * --------------------------------------------------------------------------------------------- */
+
+/* All entries of this section score PLANES: H x W float32 images with contiguous rows, plane p of an input starting
+ * p * plane_stride ELEMENTS behind its pointer (channel 0 of a [B, 3, H, W] tensor: planes = B, plane_stride = 3 * H * W, no copy);
+ * the two inputs have their own strides.  crop >= 0 drops that many pixels on every side first (util.crop_border,
+ * test_RealVSR_wi_GT.py:139) by offsetting into the plane.  Both metrics see the QUANTISED image
+ *     q(x) = uint8(rint(clamp(x, 0, 1) * 255.0f))     float32, round-half-even
+ * which is bit for bit tensor2img's clamp (utils/util.py:157) followed by train.py:301-302, (x * 255.0).round().astype(np.uint8);
+ * NaN quantises to 0 (numpy leaves that cast undefined).  No atomics, fixed summation orders: bit-identical from run to run.
+ * workspace: rvsr_metric_workspace_bytes(planes, H, W, crop) bytes serve either metric (0 for an empty shape); a smaller one is
+ * RVSR_ERR_WORKSPACE.  RVSR_ERR_BAD_ARG: null pointers, no planes or more than 65535, an empty cropped plane. */
+size_t rvsr_metric_workspace_bytes(size_t planes, int H, int W, int crop);
+/* The output tile one workgroup of the SSIM kernel computes (tests build their edge shapes from it). */
+int rvsr_metric_tile(RVSR_HOST int* th, RVSR_HOST int* tw);
+
+/* out[i] = q(x[i]) for n contiguous floats: the quantisation on its own. */
+int rvsr_quantize_u8(const float* x, unsigned char* out, size_t n, void* stream);
+
+/* util.calculate_psnr (utils/util.py:283-290; called on channel 0 at train.py:305 and test_RealVSR_wi_GT.py:142), its device part:
+ * sse[p] = sum (q(a) - q(b))^2 over the cropped plane p, an exact 64-bit integer (device pointer, `planes` values).  The caller
+ * finishes in double: mse = sse / n, 20 log10(255 / sqrt(mse)), inf for sse == 0 -- every partial sum is an integer below 2^53, so this
+ * equals the reference's np.mean path exactly. */
+int rvsr_psnr_sse(const float* a, size_t a_plane_stride, const float* b, size_t b_plane_stride, size_t planes, int H, int W, int crop,
+                  long long* sse, void* workspace, size_t workspace_bytes, void* stream);
+
+/* util.ssim (utils/util.py:293-313; calculate_ssim :316-334, called at test_RealVSR_wi_GT.py:143), its device part: sum[p] = the sum of
+ * the SSIM map of the cropped plane p in double (device pointer, `planes` values); the caller divides by (Hc - 10) (Wc - 10).
+ * Window: the outer product of cv2.getGaussianKernel(11, 1.5) = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, evaluated separably (11 + 11 taps
+ * for each of mu1, mu2, E[x^2], E[y^2], E[xy]) in double on the quantised values; 'valid' region; C1 = (0.01 * 255)^2,
+ * C2 = (0.03 * 255)^2.  Identical inputs give exactly (Hc - 10) (Wc - 10).  A cropped plane below 11 x 11 is RVSR_ERR_BAD_ARG. */
+int rvsr_ssim_sum(const float* a, size_t a_plane_stride, const float* b, size_t b_plane_stride, size_t planes, int H, int W, int crop,
+                  double* sum, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);
  * out: workgroups x 512 floats (checksums).  MFMA work issued = workgroups * 8 waves * iters * 8 * 32768 FLOP. */

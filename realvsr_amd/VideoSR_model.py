@@ -171,6 +171,16 @@ class VideoSRModel:
             out['GT'] = self.var_H.detach()[0].float().cpu()
         return out
 
+    def get_current_metrics(self, ssim=False, crop_border=0):
+        """After feed_data + test(): {'psnr': [per sample], 'ssim': [per sample]} of fake_H against the GT (the centre frame of a
+        five-dimensional var_H) on channel 0 -- the numbers the validation loop of codes/train.py:285-305 gets out of
+        get_current_visuals + tensor2img + calculate_psnr, computed on the device (realvsr_amd.metrics): only the scalars come back."""
+        from . import metrics
+        gt = self.var_H[:, self.var_L.size(1) // 2] if self.var_H.dim() == 5 else self.var_H
+        res = metrics.frame_metrics(self.fake_H.detach(), gt.detach(), crop_border=crop_border, ssim=ssim)
+        res.setdefault('ssim', [])
+        return res
+
     def get_current_learning_rate(self):
         return [g['lr'] for g in self.optimizers[0].param_groups]
 
@@ -383,6 +393,7 @@ class VideoSRGANModel:
 
     load_network = VideoSRModel.load_network
     save_network = VideoSRModel.save_network
+    get_current_metrics = VideoSRModel.get_current_metrics
 
 
 def create_model(opt):

@@ -20,7 +20,7 @@ _lib = None
 c_fp = ctypes.c_void_p  # device pointers travel as void*
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t}
 _RETURNS = dict(_SCALARS, **{'void': None, 'char*': ctypes.c_char_p})
-_POINTEES = {'void', 'float', 'int', 'long long', 'unsigned', 'unsigned char'}   # what an unmarked pointer may point at
+_POINTEES = {'void', 'float', 'double', 'int', 'long long', 'unsigned', 'unsigned char'}   # what an unmarked pointer may point at
 _HOST_OUT = {'int*': ctypes.POINTER(ctypes.c_int), 'long long*': ctypes.POINTER(ctypes.c_longlong)}   # behind the header's RVSR_HOST marker
 
 

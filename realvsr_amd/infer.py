@@ -14,7 +14,8 @@ per window the frame appears in (N times).  The outputs are identical, bit for b
 every window: the kernels are deterministic per sample and the per-frame stage does not look at its neighbours.
 
 Unlike the reference helpers the outputs stay on the GPU (the reference moves every f32 output to the host,
-`.cpu()`, utils/util.py:236): use `ycbcr_to_bgr_u8` to bring back 3 bytes per pixel.
+`.cpu()`, utils/util.py:236): use `ycbcr_to_bgr_u8` to bring back 3 bytes per pixel, and `evaluate_clip` (realvsr_amd.metrics) to score
+a clip against its ground truth with only the per-frame scalars crossing to the host.
 """
 import ctypes
 
@@ -189,3 +190,26 @@ class SlidingWindowRunner(object):
             idx = torch.tensor(index_generation(t, T, self.N, self.padding), device=clip.device)
             outs.append(fwd(self.net, clip.index_select(0, idx).unsqueeze(0)))
         return torch.cat(outs, 0)
+
+
+def evaluate_clip(runner, clip, gt, crop_border=0, ssim=True):
+    """Super-resolve `clip` [T, C, H, W] with a SlidingWindowRunner and score every frame against `gt` [T, C, sH, sW] on the device:
+    the per-clip part of codes/test_RealVSR_wi_GT.py:113-168 (channel 0, crop_border, PSNR and SSIM per frame, then the centre / border /
+    total averages with border_frame = N // 2, :58).  A runner around a network without `extract_features` (anything but EDVR) goes
+    through `reference_order`, one network call per window.  Only the scalars leave the device.
+    Returns {'psnr': [T], 'ssim': [T], 'psnr_avg', 'psnr_center', 'psnr_border', 'ssim_avg', 'ssim_center', 'ssim_border'} (the
+    'ssim*' keys only with ssim=True)."""
+    from . import metrics
+    _need_cuda(clip, gt)
+    if hasattr(runner.net, 'extract_features'):
+        out = runner(clip)
+    else:
+        with torch.no_grad():
+            out = runner.reference_order(clip)
+    if gt.dim() != 4 or gt.shape[0] != out.shape[0] or gt.shape[2:] != out.shape[2:]:
+        raise RuntimeError('evaluate_clip: gt %s does not match the output %s' % (tuple(gt.shape), tuple(out.shape)))
+    res = metrics.frame_metrics(out, gt, crop_border=crop_border, ssim=ssim)
+    for name in list(res):
+        for k, v in metrics.center_border_average(res[name], runner.N // 2).items():
+            res['%s_%s' % (name, k)] = v
+    return res
