@@ -675,6 +675,36 @@ int rvsr_psnr_sse(const float* a, size_t a_plane_stride, const float* b, size_t 
 int rvsr_ssim_sum(const float* a, size_t a_plane_stride, const float* b, size_t b_plane_stride, size_t planes, int H, int W, int crop,
                   double* sum, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 12. Batch assembly (codes/data/RealVSR_dataset.py:142-172, 309-341, codes/data/util.py:86-122, 261-276)
+ * --------------------------------------------------------------------------------------------- */
+
+/* Packed uint8 frame crops -> the float32 batch, in one launch: what the reference's data package computes per sample on the host
+ * (read_img's astype(np.float32) / 255., util.augment, np.stack, [2, 1, 0], HWC -> CHW, ascontiguousarray).
+ *   src   uint8 [samples][frames][Hs][Ws][C], contiguous, at ANY byte alignment (read with 16-byte loads aligned down; no load is
+ *         issued from an aligned 16-byte block that holds no source byte)
+ *   dst   float32 [samples][frames][C][Ho][Wo], fully overwritten, nothing outside it written; 16-byte aligned for the vector stores
+ *         (rvsr_assemble_plan), 4-byte aligned at least
+ *   flags one int per sample (device memory) or NULL: bit 0 hflip, bit 1 vflip, bit 2 rot90, applied in the order of util.augment,
+ *             a[y][x] = s[vflip ? Hs-1-y : y][hflip ? Ws-1-x : x],   out[y][x] = rot90 ? a[x][y] : a[y][x]
+ *         With flags, Hs == Ws is required (RVSR_ERR_UNSUPPORTED otherwise; the reference's np.stack needs the same).  NULL: no flips,
+ *         any Hs x Ws (whole validation frames).  Ho = Hs, Wo = Ws.
+ *   C     1 or 3 (else RVSR_ERR_UNSUPPORTED)
+ *   mode  RVSR_ASM_REVERSE: output plane c reads source channel C-1-c (the [2, 1, 0] of RealVSR_dataset.py:337-339, util.py:120).
+ *         RVSR_ASM_TO_YCBCR (C == 3 only): the source holds raw colour bytes, in the order B, G, R with RVSR_ASM_REVERSE (cv2) and
+ *         R, G, B without (PIL); the output planes are (Y, Cb, Cr) of util.bgr2ycbcr(uint8, only_y=False) (util.py:351-373) ROUNDED TO
+ *         uint8 as scripts/prepare_data.py:42-45 stores them, then normalised -- in exact integers:
+ *             v = 65481 R + 128553 G + 24966 B + 16 * 255000   (Cb: -37797, -74203, 112000, 128 * 255000;  Cr: 112000, -93786, -18214,
+ *             128 * 255000),   value = v / 255000 rounded half to even.
+ * The value map is float(u8) / 255.f correctly rounded: numpy's x.astype(np.float32) / 255. for all 256 values. */
+#define RVSR_ASM_REVERSE 1
+#define RVSR_ASM_TO_YCBCR 2
+int rvsr_assemble_clips(const unsigned char* src, float* dst, const int* flags, size_t samples, int frames, int C, int Hs, int Ws,
+                        int mode, void* stream);
+/* The plan of that call (pure host code; the same shape checks): *variant = 1 for 16-byte stores (Ws % 4 == 0 and dst 16-byte aligned),
+ * 0 for scalar stores; *blocks = workgroups (one per 64 x 64 output tile of an image). */
+int rvsr_assemble_plan(const float* dst, size_t samples, int frames, int C, int Hs, int Ws, RVSR_HOST int* variant, RVSR_HOST int* blocks);
+
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);
  * out: workgroups x 512 floats (checksums).  MFMA work issued = workgroups * 8 waves * iters * 8 * 32768 FLOP. */

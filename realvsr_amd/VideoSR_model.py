@@ -24,6 +24,7 @@ import torch
 from . import VideoSR_archs as networks
 from . import augment as augments
 from . import loss as L
+from .data import feed_packed
 from .dist import BucketedGradAllReduce, broadcast_parameters
 from .optim import FlatAdam
 
@@ -102,6 +103,11 @@ class VideoSRModel:
 
     # ------------------------------------------------------------------ data
     def feed_data(self, data, need_GT=True):
+        if data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data: the f32 batch is assembled on the device
+            self.var_L, var_H = feed_packed(data, self.device, need_GT)
+            if need_GT:
+                self.var_H = var_H
+            return
         self.var_L = data['LQs'].to(self.device)
         if need_GT:
             self.var_H = data['GT'].to(self.device)
@@ -268,6 +274,11 @@ class VideoSRGANModel:
 
     # ------------------------------------------------------------------ data
     def feed_data(self, data, need_GT=True):
+        if data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data (a packed 'ref' is not defined: the GT is the reference)
+            self.var_L, var_H = feed_packed(data, self.device, need_GT)
+            if need_GT:
+                self.var_H = self.var_ref = var_H
+            return
         self.var_L = data['LQs'].to(self.device)
         if need_GT:
             self.var_H = data['GT'].to(self.device)

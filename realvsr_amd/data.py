@@ -1,0 +1,338 @@
+"""The input side of a training step: RealVSR clips as packed uint8 crops, assembled into the f32 batch on the device.
+
+Mirrors codes/data/RealVSR_dataset.py (RealVSRDataset :15-177, RealVSRAllPairDataset :180-346) and the part of codes/data/util.py they
+use (read_img :86-101, read_img_seq :104-122, augment :261-276), split where the bytes stop being integers:
+
+  host (this module, numpy / CPU torch only)     choose the frames, draw the crop and the flips from `random` in the reference's order
+                                                 (draw_sample), copy S uint8 rows per frame into pinned memory (ClipBatchStager)
+  device (csrc/batch_kernels.hip)                float(u8) / 255, hflip / vflip / rot90, [2, 1, 0], HWC -> CHW, one launch per tensor
+                                                 (assemble_batch); optionally the YCbCr conversion of scripts/prepare_data.py
+
+The reference converts every WHOLE 1024 x 512 x 3 frame to float32 before it crops (util.py:95) and ships f32 over PCIe; here a quarter
+of the bytes cross and no float is touched on the host.  Without the conversion the result equals the reference's chain bit for bit
+(one correctly rounded division and a permutation); tests/test_data_host.py and tests/test_gpu_batch.py hold that with ==.
+
+The datasets never load the HIP library or touch the device, so they are safe in DataLoader workers.
+"""
+import os
+import pickle
+import random
+
+import numpy as np
+import torch
+
+RVSR_ASM_REVERSE = 1    # include/realvsr_hip.h, section 12 (tests/test_data_host.py holds the two copies together)
+RVSR_ASM_TO_YCBCR = 2
+FLAG_HFLIP, FLAG_VFLIP, FLAG_ROT90 = 1, 2, 4
+FRAME_CHW = (3, 1024, 512)   # the size the reference hard-codes for the crop range (RealVSR_dataset.py:121, 130, 284, 297)
+LAST_FRAME = 49              # clips have 50 frames (RealVSR_dataset.py:89, 105)
+
+
+def _refuse_lr_input(opt):
+    if opt['GT_size'] != opt['LQ_size']:
+        raise NotImplementedError('LR_input (GT_size %r != LQ_size %r: scale > 1 crops) is not built; every shipped option file has '
+                                  'scale 1' % (opt['GT_size'], opt['LQ_size']))
+
+
+def draw_sample(opt, key, rng=random, frame_chw=FRAME_CHW):
+    """The random choices of one RealVSRDataset / RealVSRAllPairDataset sample for `key` ('017_00023'), drawn from `rng` in exactly the
+    order of the reference's __getitem__ (RealVSR_dataset.py:72-163, 235-330; both classes draw alike):
+      1. rng.choice(interval_list)
+      2. border_mode: [random() < 0.5 and choice([0, 1])] under random_reverse      (:84-102)
+         else:        the `while ... randint(0, 49)` redraw of the centre, then [random() < 0.5] under random_reverse   (:103-115)
+      3. phase 'train': randint for the crop's row, then its column                  (:154-155)
+      4. util.augment's three short-circuited draws: use_flip and random(), use_rot and random(), use_rot and random()   (util.py:263-265)
+    Returns a dict: name_a (sequence), neighbor_list (frame indices of the LQ window -- and of the GT window of the all-pair class),
+    center (the five-digit name of the single GT frame of RealVSRDataset), rnd_h, rnd_w (None outside phase 'train'), size, flags
+    (bit 0 hflip, bit 1 vflip, bit 2 rot90), key."""
+    _refuse_lr_input(opt)
+    name_a, name_b = key.split('_')
+    center = int(name_b)
+    N = opt['N_frames']
+    half = N // 2
+    interval = rng.choice(opt['interval_list'])
+    if opt['border_mode']:
+        direction = 1
+        if opt['random_reverse'] and rng.random() < 0.5:
+            direction = rng.choice([0, 1])
+        if center + interval * (N - 1) > LAST_FRAME:
+            direction = 0
+        elif center - interval * (N - 1) < 0:
+            direction = 1
+        step = interval if direction == 1 else -interval
+        neighbor_list = list(range(center, center + step * N, step))
+        name_b = '{:05d}'.format(neighbor_list[0])
+    else:
+        while center + half * interval > LAST_FRAME or center - half * interval < 0:
+            center = rng.randint(0, LAST_FRAME)
+        neighbor_list = list(range(center - half * interval, center + half * interval + 1, interval))
+        if opt['random_reverse'] and rng.random() < 0.5:
+            neighbor_list.reverse()
+        name_b = '{:05d}'.format(neighbor_list[half])
+    assert len(neighbor_list) == N, 'Wrong length of neighbor list: {}'.format(len(neighbor_list))
+    rnd_h = rnd_w = None
+    flags = 0
+    if opt['phase'] == 'train':
+        _, H, W = frame_chw
+        size = opt['GT_size']
+        rnd_h = rng.randint(0, max(0, H - size))
+        rnd_w = rng.randint(0, max(0, W - size))
+        if opt['use_flip'] and rng.random() < 0.5:
+            flags |= FLAG_HFLIP
+        if opt['use_rot'] and rng.random() < 0.5:
+            flags |= FLAG_VFLIP
+        if opt['use_rot'] and rng.random() < 0.5:
+            flags |= FLAG_ROT90
+    return {'key': key, 'name_a': name_a, 'neighbor_list': neighbor_list, 'center': name_b, 'rnd_h': rnd_h, 'rnd_w': rnd_w,
+            'size': opt['GT_size'] if rnd_h is not None else None, 'flags': flags}
+
+
+def crop_u8(frame, plan):
+    """The plan's S x S crop of one uint8 frame [H, W] or [H, W, C] as a view [S, S, C] (the whole frame outside phase 'train').
+    Raises ValueError if the crop leaves the frame: the reference would build ragged arrays and fail in np.stack."""
+    if frame.dtype != np.uint8:
+        raise ValueError('frames are uint8, got %s' % frame.dtype)
+    if frame.ndim == 2:
+        frame = frame[:, :, None]
+    if frame.shape[2] > 3:
+        frame = frame[:, :, :3]   # (some images have 4 channels: util.py:98-100)
+    if plan['rnd_h'] is not None:
+        h, w, S = plan['rnd_h'], plan['rnd_w'], plan['size']
+        if h < 0 or w < 0 or h + S > frame.shape[0] or w + S > frame.shape[1]:
+            raise ValueError('the %d x %d crop at (%d, %d) leaves the %d x %d frame' % (S, S, h, w, frame.shape[0], frame.shape[1]))
+        frame = frame[h:h + S, w:w + S]
+    return frame
+
+
+class ClipBatchStager(object):
+    """Pinned staging of one batch of uint8 crops, `slots` deep.  A slot is ONE uint8 block holding, in this order, the flags
+    (int32 [B]), LQ [B, frames_lq, S, S, C] and GT [B, frames_gt, S, S, C] (frames_gt = N for the all-pair class, 1 otherwise), so a
+    batch crosses PCIe in a single copy; LQ and GT therefore start at whatever byte the sizes give (the kernel takes any alignment).
+        for i, plan in enumerate(plans): stager.stage(i, lq_frames, gt_frames, plan)      # integer slicing only
+        lq, gt, flags = stager.upload()                                                   # non_blocking, current stream
+        var_L, var_H = assemble_batch(lq, flags), assemble_batch(gt, flags)
+    upload() moves on to the next slot, so staging batch k+1 overlaps step k; before a slot is written again the copy issued from it
+    `slots` uploads ago is waited for.  pin=False keeps everything in pageable host memory (host tests; upload() is then unavailable)."""
+
+    def __init__(self, batch, frames_lq, frames_gt, size, C, pin=True, slots=2):
+        self.batch, self.frames_lq, self.frames_gt, self.size, self.C = batch, frames_lq, frames_gt, size, C
+        self.pin = pin
+        n_flags = 4 * batch
+        n_lq = batch * frames_lq * size * size * C
+        n_gt = batch * frames_gt * size * size * C
+        self._cuts = (n_flags, n_flags + n_lq, n_flags + n_lq + n_gt)
+        self._host = [torch.zeros(self._cuts[2], dtype=torch.uint8, pin_memory=pin) for _ in range(slots)]
+        self._dev = [None] * slots
+        self._done = [None] * slots
+        self._slot = 0
+
+    def _views(self, block):
+        a, b, c = self._cuts
+        B, S, C = self.batch, self.size, self.C
+        return (block[a:b].view(B, self.frames_lq, S, S, C), block[b:c].view(B, self.frames_gt, S, S, C), block[:a].view(torch.int32))
+
+    def host_views(self):
+        """(LQ, GT, flags) of the slot being staged, as CPU tensors sharing its memory."""
+        return self._views(self._host[self._slot])
+
+    def stage(self, i, lq_frames_u8, gt_frames_u8, plan):
+        """Sample i of the batch: the plan's crop of every frame (numpy uint8 [H, W, C], in the byte order the files hold)."""
+        if len(lq_frames_u8) != self.frames_lq or len(gt_frames_u8) != self.frames_gt:
+            raise ValueError('expected %d LQ and %d GT frames, got %d and %d'
+                             % (self.frames_lq, self.frames_gt, len(lq_frames_u8), len(gt_frames_u8)))
+        lq, gt, flags = (v.numpy() for v in self.host_views())
+        for dst, frames in ((lq[i], lq_frames_u8), (gt[i], gt_frames_u8)):
+            for n, frame in enumerate(frames):
+                crop = crop_u8(frame, plan)
+                if crop.shape != dst[n].shape:
+                    raise ValueError('the crop is %s, the stager holds %s' % (crop.shape, dst[n].shape))
+                dst[n] = crop
+        flags[i] = plan['flags']
+
+    def upload(self):
+        """Copy the staged slot to the device (non_blocking, current stream) -> device views (LQ uint8, GT uint8, flags int32)."""
+        if not self.pin:
+            raise RuntimeError('ClipBatchStager(pin=False) is for host tests: there is nothing to upload from')
+        s = self._slot
+        if self._dev[s] is None:
+            self._dev[s] = torch.empty(self._cuts[2], dtype=torch.uint8, device='cuda')
+        self._dev[s].copy_(self._host[s], non_blocking=True)
+        self._done[s] = torch.cuda.Event()
+        self._done[s].record()
+        self._slot = (s + 1) % len(self._host)
+        if self._done[self._slot] is not None:
+            self._done[self._slot].synchronize()   # (issued `slots` uploads ago)
+        return self._views(self._dev[s])
+
+
+def assemble_batch(u8, flags=None, mode=RVSR_ASM_REVERSE, out=None):
+    """uint8 [B, F, Hs, Ws, C] on the GPU -> float32 [B, F, C, Ho, Wo] (rvsr_assemble_clips, include/realvsr_hip.h section 12).
+    flags: int32 [B] on the GPU (bit 0 hflip, bit 1 vflip, bit 2 rot90; square crops only) or None; mode: RVSR_ASM_REVERSE |
+    RVSR_ASM_TO_YCBCR.  `u8` may start at any byte (a view into a larger block); it has to be contiguous."""
+    from . import _lib
+    from ._lib import _p, _stream
+    if not torch.is_tensor(u8) or not u8.is_cuda:
+        raise RuntimeError('assemble_batch runs on MI355X (HIP) tensors only')
+    if u8.dtype != torch.uint8 or u8.dim() != 5:
+        raise RuntimeError('assemble_batch: expected uint8 [B, F, H, W, C], got %s %s' % (u8.dtype, tuple(u8.shape)))
+    if not u8.is_contiguous():
+        raise RuntimeError('assemble_batch: the packed tensor has to be contiguous')
+    B, F, Hs, Ws, C = u8.shape
+    if flags is not None:
+        if not flags.is_cuda or flags.device != u8.device or flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() != B:
+            raise RuntimeError('assemble_batch: flags have to be a contiguous int32 [B] tensor on the device of the frames')
+    if out is None:
+        out = torch.empty(B, F, C, Hs, Ws, dtype=torch.float32, device=u8.device)
+    elif (not out.is_cuda or out.device != u8.device or out.dtype != torch.float32 or not out.is_contiguous()
+          or tuple(out.shape) != (B, F, C, Hs, Ws)):
+        raise RuntimeError('assemble_batch: out has to be a contiguous float32 %s tensor on the device of the frames' % ((B, F, C, Hs, Ws),))
+    if out.numel() == 0:
+        raise RuntimeError('assemble_batch: empty shape %s' % (tuple(u8.shape),))
+    with torch.cuda.device(u8.device):
+        _lib.check(_lib.lib().rvsr_assemble_clips(_p(u8), _p(out), _p(flags), B, F, C, Hs, Ws, int(mode), _stream()), 'assemble_clips')
+    return out
+
+
+def assemble_plan(out_ptr_or_tensor, B, F, C, Hs, Ws):
+    """(variant, workgroups) of the assemble_batch call that writes there: variant 1 = 16-byte stores, 0 = scalar stores."""
+    import ctypes
+    from . import _lib
+    ptr = out_ptr_or_tensor.data_ptr() if torch.is_tensor(out_ptr_or_tensor) else int(out_ptr_or_tensor)
+    variant, blocks = ctypes.c_int(-1), ctypes.c_int(-1)
+    _lib.check(_lib.lib().rvsr_assemble_plan(ctypes.c_void_p(ptr), B, F, C, Hs, Ws, ctypes.byref(variant), ctypes.byref(blocks)),
+               'assemble_plan')
+    return variant.value, blocks.value
+
+
+def clip_from_u8(frames_u8, mode=RVSR_ASM_REVERSE):
+    """uint8 [T, H, W, C] (GPU; C = 1 or 3, in cv2's byte order for the default mode) -> float32 [T, C, H, W]: util.read_img_seq
+    (codes/data/util.py:104-122) for the validation / test scripts, without the f32 frames on the host."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dim() != 4:
+        raise RuntimeError('clip_from_u8: expected uint8 [T, H, W, C]')
+    return assemble_batch(frames_u8.unsqueeze(0), None, mode)[0]
+
+
+def feed_packed(data, device, need_GT=True):
+    """The uint8 branch of the models' feed_data: {'LQs': uint8 [B, N, S, S, C], 'GT': uint8 [B, N | 1, S, S, C], 'flags': [B] ints,
+    optional 'mode'} -> (var_L [B, N, C, H, W], var_H [B, N, C, H, W] or [B, C, H, W] for a single GT frame; None without need_GT)."""
+    mode = data.get('mode', RVSR_ASM_REVERSE)
+    if torch.is_tensor(mode):
+        mode = mode.reshape(-1)[0]
+    mode = int(mode)
+    lq = data['LQs']
+    flags = data.get('flags')
+    if flags is not None:
+        flags = torch.as_tensor(flags)
+        if lq.shape[2] != lq.shape[3]:   # whole frames (validation): nothing was flipped
+            if not flags.is_cuda and bool((flags != 0).any()):
+                raise RuntimeError('feed_data: flips / rot90 need square crops, got %d x %d' % (lq.shape[2], lq.shape[3]))
+            flags = None
+        else:
+            flags = flags.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+    var_L = assemble_batch(lq.to(device, non_blocking=True).contiguous(), flags, mode)
+    var_H = None
+    if need_GT:
+        var_H = assemble_batch(data['GT'].to(device, non_blocking=True).contiguous(), flags, mode)
+        if var_H.size(1) == 1:
+            var_H = var_H[:, 0]
+    return var_L, var_H
+
+
+# ---------------------------------------------------------------------------------------------------------------- datasets
+def _read_png_u8(path):
+    """A file as cv2.imread(path, IMREAD_UNCHANGED) holds it for 8-bit grey / colour images: uint8 [H, W] or [H, W, 3] in B, G, R
+    order -- read through PIL (R, G, B), reversed as a view; the copy happens once, on the crop."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ('L', 'RGB'):
+            im = im.convert('RGB')
+        a = np.asarray(im)
+    return a if a.ndim == 2 else a[:, :, ::-1]
+
+
+class _RealVSRBase(torch.utils.data.Dataset):
+    """What the two classes share.  Option keys as in the reference: interval_list, random_reverse, N_frames, dataroot_GT, dataroot_LQ,
+    data_type ('img' | 'lmdb'), GT_size, LQ_size, cache_keys, border_mode, phase, use_flip, use_rot, scale, color; one key of
+    its own, frame_chw, replaces the (3, 1024, 512) the reference hard-codes for the crop range (data sets of another frame size).
+
+    A sample is {'LQs': uint8 [N, S, S, C], 'GT': uint8 [N | 1, S, S, C], 'flags': int, 'key': str} in cv2's byte order (whole frames
+    and flags 0 outside phase 'train'); torch's default collate stacks them, and VideoSRModel.feed_data takes the collated batch as it
+    is.  Only integers are touched here: no float conversion, no flip, no transposition -- those are the device's (assemble_batch).
+
+    Worker processes never load the HIP library or touch the device.  Keep it that way in subclasses: the shared MI355X machines cap
+    the number of processes that have the GPU open at 16, and a DataLoader's workers count against nothing as long as they stay on the CPU."""
+    ALL_PAIR = False
+
+    def __init__(self, opt):
+        super(_RealVSRBase, self).__init__()
+        self.opt = opt
+        _refuse_lr_input(opt)
+        self.GT_root, self.LQ_root = opt['dataroot_GT'], opt['dataroot_LQ']
+        self.data_type = opt['data_type']
+        if opt.get('color'):
+            raise NotImplementedError("opt['color'] = %r: the data sets are stored pre-converted (channel_convert is a no-op for every "
+                                      'shipped option file)' % (opt['color'],))
+        if self.data_type == 'lmdb':
+            import lmdb  # noqa: F401  (ImportError if the module is not installed)
+            with open(os.path.join(opt['dataroot_GT'], 'meta_info.pkl'), 'rb') as f:
+                self.paths_GT = pickle.load(f)['keys']
+        elif self.data_type == 'img':
+            if not opt.get('cache_keys'):
+                raise ValueError('Need to create cache keys (meta_info.pkl) by running [create_lmdb.py]')
+            with open(opt['cache_keys'], 'rb') as f:
+                self.paths_GT = pickle.load(f)['keys']
+        else:
+            raise ValueError('Wrong data type: {}'.format(self.data_type))
+        self.paths_GT = self._remove_test_sequences(self.paths_GT)
+        assert self.paths_GT, 'Error: GT path is empty.'
+        self.GT_env = self.LQ_env = None
+
+    def _read(self, which, name_a, frame):
+        """One whole frame, uint8, in cv2's byte order."""
+        if self.data_type == 'lmdb':
+            if self.GT_env is None:
+                import lmdb
+                self.GT_env = lmdb.open(self.opt['dataroot_GT'], readonly=True, lock=False, readahead=False, meminit=False)
+                self.LQ_env = lmdb.open(self.opt['dataroot_LQ'], readonly=True, lock=False, readahead=False, meminit=False)
+            with (self.GT_env if which == 'GT' else self.LQ_env).begin(write=False) as txn:
+                buf = txn.get('{}_{}'.format(name_a, frame).encode('ascii'))
+            C, H, W = FRAME_CHW
+            return np.frombuffer(buf, dtype=np.uint8).reshape(H, W, C)
+        return _read_png_u8(os.path.join(self.GT_root if which == 'GT' else self.LQ_root, name_a, frame + '.png'))
+
+    def __getitem__(self, index):
+        key = self.paths_GT[index]
+        plan = draw_sample(self.opt, key, frame_chw=self.opt.get('frame_chw') or FRAME_CHW)
+        names = ['{:05d}'.format(v) for v in plan['neighbor_list']]
+        gt_names = names if self.ALL_PAIR else [plan['center']]
+        # (np.stack copies the crops -- 3 S^2 bytes each -- which also drops the reversed-channel view of _read_png_u8)
+        gt = np.stack([crop_u8(self._read('GT', plan['name_a'], n), plan) for n in gt_names], axis=0)
+        lq = np.stack([crop_u8(self._read('LQ', plan['name_a'], n), plan) for n in names], axis=0)
+        return {'LQs': torch.from_numpy(lq), 'GT': torch.from_numpy(gt), 'flags': plan['flags'], 'key': key}
+
+    def __len__(self):
+        return len(self.paths_GT)
+
+
+class RealVSRDataset(_RealVSRBase):
+    """RealVSRDataset of codes/data/RealVSR_dataset.py:15-177: N LQ frames and the GT of the centre frame; the fifty test sequences the
+    reference hard-codes (:51-58) are left out."""
+    TEST_SEQUENCES = ('008', '026', '029', '031', '042', '055', '058', '077', '105', '113', '132', '135', '146', '155', '161', '167', '173',
+                      '175', '180', '181', '189', '194', '195', '226', '232', '237', '241', '242', '247', '256', '268', '275', '293', '309',
+                      '358', '371', '372', '379', '383', '401', '409', '413', '426', '438', '448', '471', '478', '484', '490', '498')
+
+    def _remove_test_sequences(self, keys):
+        return [v for v in keys if v.split('_')[0] not in self.TEST_SEQUENCES]
+
+
+class RealVSRAllPairDataset(_RealVSRBase):
+    """RealVSRAllPairDataset of codes/data/RealVSR_dataset.py:180-346: N LQ frames and the N GT frames of the same window;
+    opt['remove_list'] names a pickle of sequences to leave out (:216-221)."""
+    ALL_PAIR = True
+
+    def _remove_test_sequences(self, keys):
+        if self.opt.get('remove_list'):
+            with open(self.opt['remove_list'], 'rb') as f:
+                remove = pickle.load(f)
+            return [v for v in keys if v.split('_')[0] not in remove]
+        return keys

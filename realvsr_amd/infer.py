@@ -22,6 +22,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .data import clip_from_u8   # noqa: F401  (read_img_seq for the test scripts: uint8 [T, H, W, C] -> f32 [T, C, H, W] on the device)
 from .functional import _need_cuda, _p, _stream
 
 
