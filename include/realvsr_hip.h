@@ -705,6 +705,50 @@ int rvsr_assemble_clips(const unsigned char* src, float* dst, const int* flags, 
  * 0 for scalar stores; *blocks = workgroups (one per 64 x 64 output tile of an image). */
 int rvsr_assemble_plan(const float* dst, size_t samples, int frames, int C, int Hs, int Ws, RVSR_HOST int* variant, RVSR_HOST int* blocks);
 
+/* ---------------------------------------------------------------------------------------------
+ * 13. Bicubic degradation of uint8 frames (codes/scripts/generate_LR_BI_Vimeo90K.m:28, codes/data/util.py:511-710)
+ * --------------------------------------------------------------------------------------------- */
+
+/* MATLAB's antialiased bicubic imresize (cubic with a = -0.5, stretched by `scale` when shrinking; symmetric reflection at the
+ * borders) at the factors 1 / scale and scale, scale = 2 or 4, on uint8 frames, in exact integers: the LQ frames the reference's
+ * Vimeo-90K runs read from a second copy of the data set, computed from the GT bytes instead.  At these factors every normalised
+ * weight is k / 2^n:
+ *     x 1/2   [-3, -9, 29, 111, 111, 29, -9, -3] / 256                     at inputs 2 j - 3 .. 2 j + 4 of output j
+ *     x 2     [-3, 29, 111, -9] / 128 at inputs m - 2 .. m + 1 of output 2 m,   [-9, 111, 29, -3] / 128 at m - 1 .. m + 2 of 2 m + 1
+ *     x 1/4   [-7, -45, -75, -49, 93, 399, 745, 987, 987, 745, 399, 93, -49, -75, -45, -7] / 4096   at inputs 4 j - 6 .. 4 j + 9
+ *     x 4     [-45, 399, 745, -75], [-7, 93, 987, -49] / 1024 at m - 2 .. m + 1 of outputs 4 m, 4 m + 1;
+ *             [-49, 987, 93, -7], [-75, 745, 399, -45] / 1024 at m - 1 .. m + 2 of outputs 4 m + 2, 4 m + 3
+ * so a value is N / 2^b with N an integer sum over the bytes (|N| < 2^53), and the byte stored is
+ *     clamp(floor((N + 2^(b-1)) / 2^b), 0, 255),     b = 16 (x 1/2), 24 (x 1/4), 30 (x 1/2 then x 2), 44 (x 1/4 then x 4);
+ * the intermediate image of a two-stage chain is NOT rounded (MATLAB's is a double).  tests/bicubic_reference.py is this definition
+ * in numpy; the reference's float32 imresize_np can differ from it, by 1, only where N / 2^b lies next to a half-integer (tests: within 1e-3).
+ *   Hf, Wf the frame: multiples of `scale` (the script's modcrop), every edge >= 2 * scale (RVSR_ERR_UNSUPPORTED otherwise: below
+ *          that one reflection no longer suffices), at most 2^24
+ *   src    uint8 [samples][frames][Hw][Ww][C], contiguous, at ANY byte alignment (byte loads): a WINDOW of each frame, rows
+ *          wy .. wy + Hw - 1 and columns wx .. wx + Ww - 1; Hw <= Hf, Ww <= Wf
+ *   S_h, S_w   the crop, at (y0, x0) of the frame; RVSR_BIC_DOWN: crop size and origin are multiples of `scale`
+ *   geom   four ints per sample (device memory), {wy, wx, y0, x0}, or NULL = all zeros (whole frames, or their top-left part)
+ *   dst    RVSR_BIC_SAME: uint8 [samples][frames][S_h][S_w][C], shrink by `scale`, then enlarge by `scale`, rounded once;
+ *          RVSR_BIC_DOWN: uint8 [samples][frames][S_h / scale][S_w / scale][C].
+ *          Either holds what the chain gives on the WHOLE frame at the crop's position: both stages reflect at the frame's borders
+ *          (the enlarging stage at those of the Hf / scale x Wf / scale intermediate image), not at the window's, so a random crop
+ *          taken through a window is bit-identical to the crop of the degraded frame.
+ *   crop   optional (NULL: not written): uint8 [samples][frames][S_h][S_w][C], the window's own bytes at the crop -- the GT crop, from
+ *          the tile the same launch has staged
+ *   C      1 or 3;  scale 2 or 4;  mode RVSR_BIC_SAME or RVSR_BIC_DOWN   (else RVSR_ERR_UNSUPPORTED)
+ * The window has to hold every frame pixel an output touches after reflection.  rvsr_bicubic_halo(scale, mode) is how far that is
+ * beyond the crop (7 / 3 at scale 2 SAME / DOWN, 15 / 6 at scale 4; derived from the tables, -1 for an unknown scale or mode); the
+ * host uploads rows [clamp(y0 - h, 0, Hf - (S_h + 2 h)), + S_h + 2 h), or the whole frame where that is smaller, and columns alike.
+ * The entry point checks the sizes (RVSR_ERR_BAD_ARG: a window smaller than that; with geom == NULL smaller than S + h).  WHERE the
+ * window and the crop sit is device data: the kernel clamps them into the frame and clamps every read into the window, so a wrong
+ * geometry gives wrong bytes, never an access outside src.  dst and crop are fully overwritten, nothing outside them is written.
+ * One workgroup per 32 x 32 (SAME) or 16 x 16 (DOWN) tile of dst of one image; one kernel variant per (scale, mode, C). */
+#define RVSR_BIC_SAME 0
+#define RVSR_BIC_DOWN 1
+int rvsr_bicubic_u8(const unsigned char* src, unsigned char* dst, unsigned char* crop, const int* geom, size_t samples, int frames, int C,
+                    int Hw, int Ww, int Hf, int Wf, int S_h, int S_w, int scale, int mode, void* stream);
+int rvsr_bicubic_halo(int scale, int mode);   /* pure host code */
+
 /* Measurement aid, not part of the reference's interface (bench.py: roofline_conv.sustained_peak): `workgroups` x 8 waves loop `iters`
  * times over 8 register-resident v_mfma_f32_32x32x16_bf16 whose operands come from `ops` (8 x 512 x 16 B of bf16: [operand][thread][8]);
  * out: workgroups x 512 floats (checksums).  MFMA work issued = workgroups * 8 waves * iters * 8 * 32768 FLOP. */

@@ -103,7 +103,7 @@ class VideoSRModel:
 
     # ------------------------------------------------------------------ data
     def feed_data(self, data, need_GT=True):
-        if data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data: the f32 batch is assembled on the device
+        if 'GT_window' in data or data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data: the f32 batch is assembled on the device
             self.var_L, var_H = feed_packed(data, self.device, need_GT)
             if need_GT:
                 self.var_H = var_H
@@ -274,7 +274,7 @@ class VideoSRGANModel:
 
     # ------------------------------------------------------------------ data
     def feed_data(self, data, need_GT=True):
-        if data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data (a packed 'ref' is not defined: the GT is the reference)
+        if 'GT_window' in data or data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data (a packed 'ref' is not defined: the GT is the reference)
             self.var_L, var_H = feed_packed(data, self.device, need_GT)
             if need_GT:
                 self.var_H = self.var_ref = var_H

@@ -10,6 +10,7 @@ Layout (mirrors the reference modules the path touches):
     realvsr_amd.util               <-> codes/utils/util.py             (pyramid helpers)
     realvsr_amd.metrics            <-> codes/utils/util.py             (calculate_psnr / calculate_ssim, on the device)
     realvsr_amd.data               <-> codes/data/RealVSR_dataset.py   (uint8 crops on the host, the f32 batch assembled on the device)
+                                   <-> codes/data/Vimeo90K_dataset.py  (the same; optionally the bicubic LQ computed on the device from GT windows)
     realvsr_amd.csrc               HIP kernels + C ABI (include/realvsr_hip.h)
 All compute runs in librealvsr_hip.so; there is no CPU or eager-PyTorch fallback.
 """

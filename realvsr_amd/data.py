@@ -12,6 +12,11 @@ The reference converts every WHOLE 1024 x 512 x 3 frame to float32 before it cro
 of the bytes cross and no float is touched on the host.  Without the conversion the result equals the reference's chain bit for bit
 (one correctly rounded division and a permutation); tests/test_data_host.py and tests/test_gpu_batch.py hold that with ==.
 
+Vimeo-90K (codes/data/Vimeo90K_dataset.py; Vimeo90kDataset, Vimeo90kAllPairDataset below) goes the same way, and can do without its
+second copy on disk: with opt['synthesize_LQ'] a sample carries a WINDOW of the GT frames (the crop plus the halo of the bicubic taps)
+and the device computes the LQ crop from it (csrc/resize_kernels.hip, bicubic_u8): MATLAB's imresize chain of
+scripts/generate_LR_BI_Vimeo90K.m in exact integers, bit-identical to cropping the degraded whole frame.
+
 The datasets never load the HIP library or touch the device, so they are safe in DataLoader workers.
 """
 import os
@@ -23,7 +28,14 @@ import torch
 
 RVSR_ASM_REVERSE = 1    # include/realvsr_hip.h, section 12 (tests/test_data_host.py holds the two copies together)
 RVSR_ASM_TO_YCBCR = 2
+RVSR_BIC_SAME = 0       # include/realvsr_hip.h, section 13 (tests/test_bicubic_host.py holds the copies together)
+RVSR_BIC_DOWN = 1
+BIC_MODES = {'same': RVSR_BIC_SAME, 'down': RVSR_BIC_DOWN}
+# what rvsr_bicubic_halo returns: 3 s / 2 for 'down', 4 s - 1 for 'same', derived from the tap tables in csrc/resize_kernels.hip and
+# tests/bicubic_reference.py (the tests hold the three together); a copy, because DataLoader workers must not load the library
+BIC_HALO = {(2, RVSR_BIC_SAME): 7, (2, RVSR_BIC_DOWN): 3, (4, RVSR_BIC_SAME): 15, (4, RVSR_BIC_DOWN): 6}
 FLAG_HFLIP, FLAG_VFLIP, FLAG_ROT90 = 1, 2, 4
+VIMEO_FRAME_CHW = (3, 256, 448)   # the size the reference hard-codes for the crop range (Vimeo90K_dataset.py:95, 102, 221, 231)
 FRAME_CHW = (3, 1024, 512)   # the size the reference hard-codes for the crop range (RealVSR_dataset.py:121, 130, 284, 297)
 LAST_FRAME = 49              # clips have 50 frames (RealVSR_dataset.py:89, 105)
 
@@ -214,11 +226,14 @@ def clip_from_u8(frames_u8, mode=RVSR_ASM_REVERSE):
 
 def feed_packed(data, device, need_GT=True):
     """The uint8 branch of the models' feed_data: {'LQs': uint8 [B, N, S, S, C], 'GT': uint8 [B, N | 1, S, S, C], 'flags': [B] ints,
-    optional 'mode'} -> (var_L [B, N, C, H, W], var_H [B, N, C, H, W] or [B, C, H, W] for a single GT frame; None without need_GT)."""
+    optional 'mode'} -> (var_L [B, N, C, H, W], var_H [B, N, C, H, W] or [B, C, H, W] for a single GT frame; None without need_GT).
+    A batch with 'GT_window' in place of 'LQs' and 'GT' (synthesize_LQ samples) has its LQ computed on the device: _feed_window."""
     mode = data.get('mode', RVSR_ASM_REVERSE)
     if torch.is_tensor(mode):
         mode = mode.reshape(-1)[0]
     mode = int(mode)
+    if 'GT_window' in data:
+        return _feed_window(data, device, need_GT, mode)
     lq = data['LQs']
     flags = data.get('flags')
     if flags is not None:
@@ -236,6 +251,140 @@ def feed_packed(data, device, need_GT=True):
         if var_H.size(1) == 1:
             var_H = var_H[:, 0]
     return var_L, var_H
+
+
+def _first_int(v):
+    return int(v.reshape(-1)[0]) if torch.is_tensor(v) else int(v)
+
+
+def _feed_window(data, device, need_GT, mode):
+    """The 'GT_window' form of feed_packed (synthesize_LQ samples of the Vimeo-90K classes): {'GT_window': uint8 [B, N, Hw, Ww, C],
+    'geom': int [B, 4], 'flags': [B] ints, 'synth_scale', 'synth_mode', 'frame_h', 'frame_w', 'crop_size', 'gt_index'} -> one
+    bicubic_u8 launch that writes the LQ crop and the GT crop, then the two assemble_batch calls of the packed path.  With
+    RVSR_ASM_TO_YCBCR the degradation runs on the raw colour bytes and the conversion after it, like the stored _ycbcr copies."""
+    win = data['GT_window'].to(device, non_blocking=True).contiguous()
+    S = _first_int(data['crop_size'])
+    frame_hw = (_first_int(data['frame_h']), _first_int(data['frame_w']))
+    geom = torch.as_tensor(data['geom']).to(dtype=torch.int32).reshape(-1, 4)
+    lq, gt = bicubic_u8(win, _first_int(data['synth_scale']), _first_int(data['synth_mode']), geom=geom, frame_hw=frame_hw,
+                        crop_hw=(S, S) if S else frame_hw, want_crop=True)   # (crop_size 0: whole frames, outside phase 'train')
+    flags = None
+    if S:
+        flags = torch.as_tensor(data['flags']).to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+    var_L = assemble_batch(lq, flags, mode)
+    var_H = None
+    if need_GT:
+        g = _first_int(data.get('gt_index', -1))
+        if g >= 0:   # the single-frame class: the GT is the crop of the centre frame only
+            gt = gt[:, g:g + 1].contiguous()
+        var_H = assemble_batch(gt, flags, mode)
+        if var_H.size(1) == 1:   # (as in feed_packed)
+            var_H = var_H[:, 0]
+    return var_L, var_H
+
+
+def bicubic_halo(scale, mode):
+    """rvsr_bicubic_halo: how many frame rows / columns beyond the crop the bicubic chain reads (host-side integers only)."""
+    mode = BIC_MODES.get(mode, mode)
+    if (scale, mode) not in BIC_HALO:
+        raise ValueError('bicubic: scale %r (2 or 4), mode %r (%s)' % (scale, mode, ' | '.join(sorted(BIC_MODES))))
+    return BIC_HALO[(scale, mode)]
+
+
+def _check_bicubic_frame(frame_hw, scale):
+    Hf, Wf = frame_hw
+    if Hf % scale or Wf % scale:
+        raise ValueError('bicubic: the %d x %d frame is no multiple of the scale %d (modcrop it first)' % (Hf, Wf, scale))
+    if Hf < 2 * scale or Wf < 2 * scale:
+        raise ValueError('bicubic: the %d x %d frame has an edge below 2 * scale = %d: one reflection no longer suffices'
+                         % (Hf, Wf, 2 * scale))
+
+
+def check_bicubic_geometry(geom, window_hw, frame_hw, crop_hw, scale, mode):
+    """The part of rvsr_bicubic_u8's contract that the entry point cannot see because geom is device memory, for one sample's
+    (wy, wx, y0, x0): crop and window inside the frame, DOWN origins at multiples of the scale, and the window holding every frame
+    pixel the crop's outputs touch after reflection.  Raises ValueError."""
+    h = bicubic_halo(scale, mode)
+    mode = BIC_MODES.get(mode, mode)
+    wy, wx, y0, x0 = (int(v) for v in geom)
+    for name, w0, W, c0, S, F in (('rows', wy, window_hw[0], y0, crop_hw[0], frame_hw[0]),
+                                  ('columns', wx, window_hw[1], x0, crop_hw[1], frame_hw[1])):
+        if S <= 0 or c0 < 0 or c0 + S > F:
+            raise ValueError('bicubic: the crop %s [%d, %d) leave the frame (%d)' % (name, c0, c0 + S, F))
+        if W > F or w0 < 0 or w0 + W > F:
+            raise ValueError('bicubic: the window %s [%d, %d) leave the frame (%d)' % (name, w0, w0 + W, F))
+        if mode == RVSR_BIC_DOWN and (c0 % scale or S % scale):
+            raise ValueError('bicubic: DOWN needs crop %s at multiples of the scale %d, got origin %d, size %d' % (name, scale, c0, S))
+        lo, hi = c0 - h, c0 + S - 1 + h        # what the outputs touch, before reflection
+        need_lo, need_hi = max(lo, 0), min(hi, F - 1)
+        if lo < 0:
+            need_lo, need_hi = 0, max(need_hi, min(-1 - lo, F - 1))
+        if hi >= F:
+            need_lo, need_hi = min(need_lo, max(2 * F - 1 - hi, 0)), F - 1
+        if w0 > need_lo or w0 + W - 1 < need_hi:
+            raise ValueError('bicubic: the window %s [%d, %d) do not cover [%d, %d], the crop plus its halo of %d after reflection'
+                             % (name, w0, w0 + W, need_lo, need_hi, h))
+
+
+def degrade_window_plan(plan, frame_hw, scale, mode):
+    """Host-side integers only: from a crop plan (rnd_h, rnd_w, size in GT frame coordinates; rnd_h None = the whole frame) the window
+    the host uploads -> ((wy, wx), (Hw, Ww), (wy, wx, y0, x0)): rows [clamp(y0 - h, 0, Hf - (S + 2 h)), + S + 2 h) with h the chain's
+    halo, or the whole frame where that is smaller, and columns alike; the last tuple is the sample's `geom` row."""
+    h = bicubic_halo(scale, mode)
+    _check_bicubic_frame(frame_hw, scale)
+    Hf, Wf = frame_hw
+    if plan['rnd_h'] is None:
+        return (0, 0), (Hf, Wf), (0, 0, 0, 0)
+    y0, x0, S = plan['rnd_h'], plan['rnd_w'], plan['size']
+    Hw, Ww = min(Hf, S + 2 * h), min(Wf, S + 2 * h)
+    wy, wx = min(max(y0 - h, 0), Hf - Hw), min(max(x0 - h, 0), Wf - Ww)
+    geom = (wy, wx, y0, x0)
+    check_bicubic_geometry(geom, (Hw, Ww), frame_hw, (S, S), scale, mode)
+    return (wy, wx), (Hw, Ww), geom
+
+
+def bicubic_u8(u8, scale, mode='same', geom=None, frame_hw=None, crop_hw=None, want_crop=False):
+    """uint8 [B, F, Hw, Ww, C] windows of frames on the GPU -> the bicubic chain's uint8 bytes at the crop (rvsr_bicubic_u8,
+    include/realvsr_hip.h section 13): mode 'same' [B, F, S_h, S_w, C] (shrink by `scale`, enlarge by `scale`, rounded once), 'down'
+    [B, F, S_h / scale, S_w / scale, C].  geom: int [B, 4] rows (wy, wx, y0, x0) -- on the host (checked here per sample, then
+    uploaded) or already on the device (then where the windows sit is the caller's contract) -- or None: the tensors are whole frames.
+    frame_hw, crop_hw default to the window's size.  want_crop: also return the window's own bytes at the crop, (dst, crop)."""
+    from . import _lib
+    from ._lib import _p, _stream
+    if not torch.is_tensor(u8) or not u8.is_cuda:
+        raise RuntimeError('bicubic_u8 runs on MI355X (HIP) tensors only')
+    if u8.dtype != torch.uint8 or u8.dim() != 5:
+        raise RuntimeError('bicubic_u8: expected uint8 [B, F, H, W, C], got %s %s' % (u8.dtype, tuple(u8.shape)))
+    if not u8.is_contiguous():
+        raise RuntimeError('bicubic_u8: the packed tensor has to be contiguous')
+    if mode not in BIC_MODES and mode not in BIC_MODES.values():
+        raise RuntimeError('bicubic_u8: mode %r (%s)' % (mode, ' | '.join(sorted(BIC_MODES))))
+    mode = BIC_MODES.get(mode, mode)
+    B, F, Hw, Ww, C = u8.shape
+    frame_hw = (Hw, Ww) if frame_hw is None else tuple(int(v) for v in frame_hw)
+    crop_hw = (Hw, Ww) if crop_hw is None else tuple(int(v) for v in crop_hw)
+    if geom is not None:
+        geom = torch.as_tensor(geom)
+        if geom.dtype != torch.int32 or tuple(geom.shape) != (B, 4):
+            raise RuntimeError('bicubic_u8: geom has to be an int32 [B, 4] tensor, got %s %s' % (geom.dtype, tuple(geom.shape)))
+        if not geom.is_cuda:
+            if (scale, mode) in BIC_HALO:   # (anything else is the entry point's refusal)
+                for row in geom.tolist():
+                    check_bicubic_geometry(row, (Hw, Ww), frame_hw, crop_hw, scale, mode)
+            geom = geom.to(u8.device, non_blocking=True)
+        elif geom.device != u8.device:
+            raise RuntimeError('bicubic_u8: geom has to be on the device of the frames')
+        geom = geom.contiguous()
+    scale = int(scale)
+    out_hw = (crop_hw[0] // scale, crop_hw[1] // scale) if mode == RVSR_BIC_DOWN and scale > 0 else crop_hw
+    if B * F * C == 0 or min(out_hw) <= 0:
+        raise RuntimeError('bicubic_u8: empty shape %s, crop %s' % (tuple(u8.shape), crop_hw))
+    dst = torch.empty((B, F) + out_hw + (C,), dtype=torch.uint8, device=u8.device)
+    crop = torch.empty((B, F) + crop_hw + (C,), dtype=torch.uint8, device=u8.device) if want_crop else None
+    with torch.cuda.device(u8.device):
+        _lib.check(_lib.lib().rvsr_bicubic_u8(_p(u8), _p(dst), _p(crop), _p(geom), B, F, C, Hw, Ww, frame_hw[0], frame_hw[1], crop_hw[0],
+                                              crop_hw[1], scale, mode, _stream()), 'bicubic_u8')
+    return (dst, crop) if want_crop else dst
 
 
 # ---------------------------------------------------------------------------------------------------------------- datasets
@@ -336,3 +485,156 @@ class RealVSRAllPairDataset(_RealVSRBase):
                 remove = pickle.load(f)
             return [v for v in keys if v.split('_')[0] not in remove]
         return keys
+
+
+def vimeo_frame_list(n_frames):
+    """Vimeo90K_dataset.py:53-56: N = 1 -> [4], 3 -> [3, 4, 5], 5 -> [2 .. 6], 7 -> [1 .. 7]."""
+    return [i + (9 - n_frames) // 2 for i in range(n_frames)]
+
+
+def draw_vimeo_sample(opt, key, frame_list, rng=random, frame_chw=VIMEO_FRAME_CHW):
+    """The random choices of one Vimeo90kDataset / Vimeo90kAllPairDataset sample, drawn from `rng` in the order of the reference's
+    __getitem__ (Vimeo90K_dataset.py:80-134, 206-262; both classes draw alike):
+      1. random_reverse and random() < 0.5: frame_list.reverse() -- IN PLACE, on the list the data set keeps (:91-92, :217-218): the
+         reversal persists into the following samples.  An oddity, but it decides which frames a seed yields.
+      2. phase 'train': randint for the crop's row, then its column -- of the LQ frame.  With LR_input (GT_size != LQ_size) that is the
+         frame shrunk by opt['scale'] and a crop of GT_size // scale (:114-121); the GT crop sits at scale times the origin.
+      3. util.augment's three short-circuited draws (util.py:263-265).
+    interval_list and border_mode are read by nobody (the reference's classes only log them).  Returns a dict: name_a, name_b,
+    frame_list (a copy, after the reversal), rnd_h, rnd_w, size (the GT crop; None outside phase 'train'), lq_h, lq_w, lq_size (the LQ
+    crop), scale (of LR_input, else 1), flags, key."""
+    name_a, name_b = key.split('_')
+    if opt['random_reverse'] and rng.random() < 0.5:
+        frame_list.reverse()
+    lr_input = opt['GT_size'] != opt['LQ_size']
+    scale = opt['scale'] if lr_input else 1
+    plan = {'key': key, 'name_a': name_a, 'name_b': name_b, 'frame_list': list(frame_list), 'rnd_h': None, 'rnd_w': None, 'size': None,
+            'lq_h': None, 'lq_w': None, 'lq_size': None, 'scale': scale, 'flags': 0}
+    if opt['phase'] == 'train':
+        _, H, W = frame_chw
+        GT_size = opt['GT_size']
+        lq_size = GT_size // scale
+        lq_h = rng.randint(0, max(0, H // scale - lq_size))
+        lq_w = rng.randint(0, max(0, W // scale - lq_size))
+        flags = 0
+        if opt['use_flip'] and rng.random() < 0.5:
+            flags |= FLAG_HFLIP
+        if opt['use_rot'] and rng.random() < 0.5:
+            flags |= FLAG_VFLIP
+        if opt['use_rot'] and rng.random() < 0.5:
+            flags |= FLAG_ROT90
+        plan.update(rnd_h=int(lq_h * scale), rnd_w=int(lq_w * scale), size=GT_size, lq_h=lq_h, lq_w=lq_w, lq_size=lq_size, flags=flags)
+    return plan
+
+
+class _Vimeo90kBase(torch.utils.data.Dataset):
+    """What the two Vimeo-90K classes share.  Option keys as in the reference: interval_list, random_reverse, N_frames, dataroot_GT,
+    dataroot_LQ, data_type ('img' | 'lmdb'), GT_size, LQ_size, cache_keys, phase, use_flip, use_rot, scale; two keys of this project's
+    own: frame_chw replaces the (3, 256, 448) the reference hard-codes, and synthesize_LQ (below).  Files are
+    <root>/<name_a>/<name_b>/im<v>.png, lmdb keys <key>_<v>.
+
+    A sample is {'LQs': uint8 [N, s, s, C], 'GT': uint8 [N | 1, S, S, C], 'flags': int, 'key': str} in cv2's byte order, s = S unless
+    LR_input (GT_size != LQ_size: s = S // scale, the LQ files are the shrunk frames); VideoSRModel.feed_data takes the collated batch.
+
+    synthesize_LQ: true -- dataroot_LQ is not read.  The LQ frames are MATLAB's bicubic chain of the GT frames, computed on the device
+    (bicubic_u8): with GT_size == LQ_size shrink-and-enlarge ('same') at opt['scale_synth'] (default 2: the shipped option files'
+    vimeo_septuplet_BIx2_same), otherwise 'down' at opt['scale'].  The sample carries, in place of 'LQs' and 'GT',
+        'GT_window'  uint8 [N, Hw, Ww, C]: the window of every frame of frame_list (crop + 2 halo per edge, or the whole frame where
+                     that is smaller; degrade_window_plan),  'geom' int32 [4]: (wy, wx, y0, x0),
+        'synth_scale', 'synth_mode', 'frame_h', 'frame_w', 'crop_size': ints,  'gt_index': the frame whose crop is the GT (the centre
+                     frame for Vimeo90kDataset), -1 = all of them (Vimeo90kAllPairDataset)
+    and feed_packed computes both tensors from it.  Outside phase 'train' the window is the whole frame.
+
+    Worker processes never load the HIP library or touch the device (see _RealVSRBase): the halo comes from BIC_HALO, not from the library."""
+    ALL_PAIR = False
+
+    def __init__(self, opt):
+        super(_Vimeo90kBase, self).__init__()
+        self.opt = opt
+        self.GT_root, self.LQ_root = opt['dataroot_GT'], opt.get('dataroot_LQ')
+        self.data_type = opt['data_type']
+        self.LR_input = opt['GT_size'] != opt['LQ_size']
+        self.synthesize = bool(opt.get('synthesize_LQ'))
+        self.frame_chw = tuple(opt.get('frame_chw') or VIMEO_FRAME_CHW)
+        self.frame_list = vimeo_frame_list(opt['N_frames'])
+        self.center = opt['N_frames'] // 2
+        if self.data_type == 'lmdb':
+            import lmdb  # noqa: F401  (ImportError if the module is not installed)
+            with open(os.path.join(opt['dataroot_GT'], 'meta_info.pkl'), 'rb') as f:
+                self.paths_GT = pickle.load(f)['keys']
+        elif opt.get('cache_keys'):
+            with open(opt['cache_keys'], 'rb') as f:
+                self.paths_GT = self._keys_of(pickle.load(f))
+        else:
+            raise ValueError('Need to create cache keys (meta_info.pkl) by running [create_lmdb.py]')
+        assert self.paths_GT, 'Error: GT path is empty.'
+        if self.data_type not in ('lmdb', 'img'):
+            raise ValueError('Wrong data type: {}'.format(self.data_type))
+        if self.synthesize:
+            self.synth_scale = int(opt['scale'] if self.LR_input else opt.get('scale_synth') or 2)
+            self.synth_mode = RVSR_BIC_DOWN if self.LR_input else RVSR_BIC_SAME
+            bicubic_halo(self.synth_scale, self.synth_mode)
+            _check_bicubic_frame(self.frame_chw[1:], self.synth_scale)
+            if self.LR_input and opt['GT_size'] % self.synth_scale:
+                raise ValueError('synthesize_LQ: GT_size %d is no multiple of the scale %d' % (opt['GT_size'], self.synth_scale))
+        self.GT_env = self.LQ_env = None
+
+    def _read(self, which, plan, v):
+        """One whole frame, uint8, in cv2's byte order."""
+        if self.data_type == 'lmdb':
+            if self.GT_env is None:
+                import lmdb
+                self.GT_env = lmdb.open(self.opt['dataroot_GT'], readonly=True, lock=False, readahead=False, meminit=False)
+                if not self.synthesize:
+                    self.LQ_env = lmdb.open(self.opt['dataroot_LQ'], readonly=True, lock=False, readahead=False, meminit=False)
+            with (self.GT_env if which == 'GT' else self.LQ_env).begin(write=False) as txn:
+                buf = txn.get('{}_{}'.format(plan['key'], v).encode('ascii'))
+            C, H, W = self.frame_chw
+            s = plan['scale'] if which == 'LQ' else 1
+            return np.frombuffer(buf, dtype=np.uint8).reshape(H // s, W // s, C)
+        return _read_png_u8(os.path.join(self.GT_root if which == 'GT' else self.LQ_root, plan['name_a'], plan['name_b'],
+                                         'im{}.png'.format(v)))
+
+    def __getitem__(self, index):
+        key = self.paths_GT[index]
+        plan = draw_vimeo_sample(self.opt, key, self.frame_list, frame_chw=self.frame_chw)
+        gt_frames = plan['frame_list'] if self.ALL_PAIR or self.synthesize else [4]   # (:99: im4, whatever N_frames)
+        if self.synthesize:
+            frame_hw = self.frame_chw[1:]
+            (wy, wx), (Hw, Ww), geom = degrade_window_plan(plan, frame_hw, self.synth_scale, self.synth_mode)
+            frames = []
+            for v in gt_frames:
+                f = self._read('GT', plan, v)
+                if f.shape[:2] != tuple(frame_hw):
+                    raise ValueError('%s frame %s is %d x %d, frame_chw says %d x %d' % ((key, v) + f.shape[:2] + tuple(frame_hw)))
+                f = f[:, :, None] if f.ndim == 2 else f[:, :, :3]
+                frames.append(f[wy:wy + Hw, wx:wx + Ww])
+            return {'GT_window': torch.from_numpy(np.stack(frames, axis=0)), 'geom': torch.tensor(geom, dtype=torch.int32),
+                    'flags': plan['flags'], 'key': key, 'synth_scale': self.synth_scale, 'synth_mode': self.synth_mode,
+                    'frame_h': frame_hw[0], 'frame_w': frame_hw[1], 'crop_size': plan['size'] if plan['size'] is not None else 0,
+                    'gt_index': -1 if self.ALL_PAIR else plan['frame_list'].index(4)}
+        lq_plan = {'rnd_h': plan['lq_h'], 'rnd_w': plan['lq_w'], 'size': plan['lq_size']}
+        gt = np.stack([crop_u8(self._read('GT', plan, v), plan) for v in gt_frames], axis=0)
+        lq = np.stack([crop_u8(self._read('LQ', plan, v), lq_plan) for v in plan['frame_list']], axis=0)
+        return {'LQs': torch.from_numpy(lq), 'GT': torch.from_numpy(gt), 'flags': plan['flags'], 'key': key}
+
+    def __len__(self):
+        return len(self.paths_GT)
+
+
+class Vimeo90kDataset(_Vimeo90kBase):
+    """Vimeo90kDataset of codes/data/Vimeo90K_dataset.py:24-147: N LQ frames and the GT of im4; cache_keys is a pickle {'keys': [...]} (:63)."""
+
+    @staticmethod
+    def _keys_of(pickled):
+        return pickled['keys']
+
+
+class Vimeo90kAllPairDataset(_Vimeo90kBase):
+    """Vimeo90kAllPairDataset of codes/data/Vimeo90K_dataset.py:150-276: N LQ frames and the N GT frames of the same list; cache_keys is a
+    pickle of the key list itself (:189)."""
+    ALL_PAIR = True
+
+    @staticmethod
+    def _keys_of(pickled):
+        return pickled
