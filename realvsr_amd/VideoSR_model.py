@@ -13,7 +13,8 @@ MI355X wiring instead of DataParallel / DistributedDataParallel + torch.optim.Ad
   * with ``opt['dist']`` every rank (one process per GPU) starts from rank 0's parameters and the gradient buffer is
     all-reduced in buckets over RCCL while backward is still running (dist.BucketedGradAllReduce);
   * augmentation runs as one kernel on the device-resident clip pair (augment.apply_augment).
-Out of scope: LR schedulers, logging, checkpoint cadence, the VGG feature loss.
+The learning-rate schedule, checkpoints and resume of codes/models/base_model.py:38-67, 121-141 are ``_TrainingState`` below, shared by
+both model classes; realvsr_amd.train is the loop that calls them.  Out of scope: the VGG feature loss.
 ``VideoSRGANModel`` below is the GAN stage (VideoSRGAN_AllPair_model_YCbCr_Split.py) on the same machinery.
 """
 import os
@@ -24,6 +25,7 @@ import torch
 from . import VideoSR_archs as networks
 from . import augment as augments
 from . import loss as L
+from . import lr_scheduler
 from .data import feed_packed
 from .dist import BucketedGradAllReduce, broadcast_parameters
 from .optim import FlatAdam
@@ -49,7 +51,76 @@ def _criterion(name, nc, role):
     raise NotImplementedError('Loss type [{:s}] is not recognized.'.format(str(name)))
 
 
-class VideoSRModel:
+class _TrainingState:
+    """What the reference's BaseModel gives its training loop (codes/models/base_model.py:38-67, 121-141; codes/train.py:141, 156,
+    326-327), for a class with ``opt``, ``optimizers``, ``schedulers``, ``netG`` and ``save_network``."""
+
+    def _build_schedulers(self, train_opt, multistep_name):
+        """One scheduler per optimizer from train_opt['lr_scheme'] (..._Split.py:127-150, VideoSRGAN_..._Split.py:163-181; the GAN
+        constructor spells the multi-step scheme 'MultiStepLR').  Without the key: no scheduler, the rate stays what the optimizer got."""
+        scheme = train_opt.get('lr_scheme')
+        if scheme is None:
+            return
+        for optimizer in self.optimizers:
+            if scheme == multistep_name:
+                sched = lr_scheduler.MultiStepLR_Restart(optimizer, train_opt['lr_steps'], restarts=train_opt.get('restarts'),
+                                                         weights=train_opt.get('restart_weights'), gamma=train_opt['lr_gamma'],
+                                                         clear_state=train_opt.get('clear_state'))
+            elif scheme == 'CosineAnnealingLR_Restart':
+                sched = lr_scheduler.CosineAnnealingLR_Restart(optimizer, train_opt['T_period'], eta_min=train_opt['eta_min'],
+                                                               restarts=train_opt.get('restarts'), weights=train_opt.get('restart_weights'))
+            else:
+                raise NotImplementedError('lr_scheme [{:s}] is not recognized ({:s} | CosineAnnealingLR_Restart)'.format(
+                    str(scheme), multistep_name))
+            # the loop steps the schedule BEFORE the optimizer (train.py:156, 160), as the reference does; torch's one-time
+            # warning about that order assumes the opposite convention
+            optimizer._opt_called = True
+            self.schedulers.append(sched)
+
+    def _set_lr(self, lr_groups_l):
+        """Set the rates for warm-up; lr_groups_l: one list of rates per optimizer."""
+        for optimizer, lr_groups in zip(self.optimizers, lr_groups_l):
+            for param_group, lr in zip(optimizer.param_groups, lr_groups):
+                param_group['lr'] = lr
+
+    def _get_init_lr(self):
+        """The initial rates, which the schedulers recorded in the groups."""
+        return [[g['initial_lr'] for g in optimizer.param_groups] for optimizer in self.optimizers]
+
+    def update_learning_rate(self, cur_iter, warmup_iter=-1):
+        """Host scalars only: the rate reaches the device as an argument of FlatAdam's kernel."""
+        for scheduler in self.schedulers:
+            scheduler.step()
+        if cur_iter < warmup_iter:
+            self._set_lr([[v / warmup_iter * cur_iter for v in init_lr_g] for init_lr_g in self._get_init_lr()])
+
+    def _networks_to_save(self):
+        return [('G', self.netG)]
+
+    def save(self, iter_step):
+        for label, network in self._networks_to_save():
+            self.save_network(network, os.path.join(self.opt['path']['models'], '{}_{}.pth'.format(iter_step, label)))
+
+    def save_training_state(self, epoch, iter_step):
+        """{'epoch', 'iter', 'schedulers', 'optimizers'} with torch.optim.Adam's state_dict layout, as the reference writes it."""
+        state = {'epoch': epoch, 'iter': iter_step, 'schedulers': [s.state_dict() for s in self.schedulers],
+                 'optimizers': [o.state_dict() for o in self.optimizers]}
+        torch.save(state, os.path.join(self.opt['path']['training_state'], '{}.state'.format(iter_step)))
+
+    def resume_training(self, resume_state):
+        """Optimizers (into the flat moments: FlatAdam.load_state_dict) and schedulers; the networks come from pretrain_model_G / _D,
+        which options.check_resume points at the checkpoint."""
+        resume_optimizers = resume_state['optimizers']
+        resume_schedulers = resume_state['schedulers']
+        assert len(resume_optimizers) == len(self.optimizers), 'Wrong lengths of optimizers'
+        assert len(resume_schedulers) == len(self.schedulers), 'Wrong lengths of schedulers'
+        for i, o in enumerate(resume_optimizers):
+            self.optimizers[i].load_state_dict(o)
+        for i, s in enumerate(resume_schedulers):
+            self.schedulers[i].load_state_dict(s)
+
+
+class VideoSRModel(_TrainingState):
     def __init__(self, opt, split=True):
         self.opt = opt
         self.split = split
@@ -95,6 +166,7 @@ class VideoSRModel:
         self.optimizer_G = FlatAdam(groups, lr=train_opt['lr_G'], weight_decay=train_opt.get('weight_decay_G') or 0,
                                     betas=(train_opt['beta1'], train_opt['beta2']))
         self.optimizers.append(self.optimizer_G)
+        self._build_schedulers(train_opt, 'MultiStepLR_Restart')
         if self.dist:
             self.reducer = BucketedGradAllReduce(None, bucket_mb=float(os.environ.get('RVSR_BUCKET_MB', train_opt.get('bucket_mb', 4.0))),
                                                  buffers=self.optimizer_G.buffers, broadcast=False,
@@ -215,14 +287,14 @@ def _gan_pixel_criterion(name, channels):
     raise NotImplementedError('Loss type [{:s}] is not recognized.'.format(str(name)))
 
 
-class VideoSRGANModel:
+class VideoSRGANModel(_TrainingState):
     """``VideoSRGANModel`` of codes/models/VideoSRGAN_AllPair_model_YCbCr_Split.py (:23-183 constructor, :185-191 feed_data, :193-317
     optimize_parameters): G = the generator of define_G, D = define_D's patch discriminator on the two high-frequency Laplacian bands
     of Y; pixel terms on the pyramid (SSIM / Charbonnier on the bands, GWLoss on CbCr) + the ('ra')GAN term, then the D step (two
     backward passes: real, fake).  Both optimizers are FlatAdam; every operator is a HIP kernel (discriminator_arch, loss.GANLoss).
     The reference's call order of D -- hence the BatchNorm running statistics -- is kept: 5 forwards per RaGAN step, 3 per vanilla step,
     2 of them skipped on steps without a G update.
-    Out of scope (NotImplementedError): the CPU path, opt['dist'], the VGG feature loss, 'lsgan' / 'wgan-gp', LR schedulers."""
+    Out of scope (NotImplementedError): the CPU path, opt['dist'], the VGG feature loss, 'lsgan' / 'wgan-gp'."""
 
     def __init__(self, opt):
         self.opt = opt
@@ -270,6 +342,7 @@ class VideoSRGANModel:
         self.optimizer_D = FlatAdam(list(self.netD.parameters()), lr=train_opt['lr_D'], weight_decay=train_opt.get('weight_decay_D') or 0,
                                     betas=(train_opt['beta1_D'], train_opt['beta2_D']))
         self.optimizers.append(self.optimizer_D)
+        self._build_schedulers(train_opt, 'MultiStepLR')
         self.log_dict = OrderedDict()
 
     # ------------------------------------------------------------------ data
@@ -401,6 +474,9 @@ class VideoSRGANModel:
             VideoSRModel.load_network(self, path['pretrain_model_G'], self.netG, strict)
         if self.is_train and path.get('pretrain_model_D') is not None:
             VideoSRModel.load_network(self, path['pretrain_model_D'], self.netD, strict)
+
+    def _networks_to_save(self):
+        return [('G', self.netG), ('D', self.netD)]
 
     load_network = VideoSRModel.load_network
     save_network = VideoSRModel.save_network

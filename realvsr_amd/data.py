@@ -46,6 +46,14 @@ def _refuse_lr_input(opt):
                                   'scale 1' % (opt['GT_size'], opt['LQ_size']))
 
 
+def _refuse_color_conversion(opt):
+    """util.channel_convert (codes/data/util.py:312-323) converts for 'gray' and 'y' (and grey files for 'RGB') and passes everything
+    else through -- 'ycbcr', what every shipped option file says, included: the data sets are stored pre-converted."""
+    if opt.get('color') in ('gray', 'y'):
+        raise NotImplementedError("opt['color'] = %r: the data sets are stored pre-converted (channel_convert is a no-op for every "
+                                  'shipped option file)' % (opt['color'],))
+
+
 def draw_sample(opt, key, rng=random, frame_chw=FRAME_CHW):
     """The random choices of one RealVSRDataset / RealVSRAllPairDataset sample for `key` ('017_00023'), drawn from `rng` in exactly the
     order of the reference's __getitem__ (RealVSR_dataset.py:72-163, 235-330; both classes draw alike):
@@ -418,9 +426,7 @@ class _RealVSRBase(torch.utils.data.Dataset):
         _refuse_lr_input(opt)
         self.GT_root, self.LQ_root = opt['dataroot_GT'], opt['dataroot_LQ']
         self.data_type = opt['data_type']
-        if opt.get('color'):
-            raise NotImplementedError("opt['color'] = %r: the data sets are stored pre-converted (channel_convert is a no-op for every "
-                                      'shipped option file)' % (opt['color'],))
+        _refuse_color_conversion(opt)
         if self.data_type == 'lmdb':
             import lmdb  # noqa: F401  (ImportError if the module is not installed)
             with open(os.path.join(opt['dataroot_GT'], 'meta_info.pkl'), 'rb') as f:
@@ -638,3 +644,166 @@ class Vimeo90kAllPairDataset(_Vimeo90kBase):
     @staticmethod
     def _keys_of(pickled):
         return pickled
+
+
+# ---------------------------------------------------------------------------------------------------------------- validation clips
+def index_generation(crt_i, max_n, N, padding='reflection'):
+    """Indices of the N frames centred on `crt_i` in a sequence of `max_n` frames (counted from 1).
+
+    padding: replicate | reflection | new_info | circle; e.g. crt_i = 0, N = 5:
+    [0, 0, 0, 1, 2] | [2, 1, 0, 1, 2] | [4, 3, 0, 1, 2] | [3, 4, 0, 1, 2]   (codes/data/util.py:169-214)."""
+    last = max_n - 1
+    half = N // 2
+    if padding not in ('replicate', 'reflection', 'new_info', 'circle'):
+        raise ValueError('Wrong padding mode')
+    idx = []
+    for i in range(crt_i - half, crt_i + half + 1):
+        if i < 0:
+            j = {'replicate': 0, 'reflection': -i, 'new_info': crt_i + half - i, 'circle': N + i}[padding]
+        elif i > last:
+            j = {'replicate': last, 'reflection': 2 * last - i, 'new_info': crt_i - half - (i - last),
+                 'circle': i - N}[padding]
+        else:
+            j = i
+        idx.append(j)
+    return idx
+
+
+
+
+class VideoTestDataset(torch.utils.data.Dataset):
+    """VideoTestDataset of codes/data/VideoTestDataset.py (the 'VideoTest' mode of every shipped option file's `val` section): the
+    sub-folders of dataroot_LQ / dataroot_GT are clips, every frame of every clip is one sample.  Option keys as in the reference: name
+    (vid4 | reds4 | realvsr_test, any case), cache_data, N_frames, padding, dataroot_GT, dataroot_LQ, data_type, color.  'lmdb' is
+    refused as there; cache_data has to be true (the reference's other branch is an empty TODO and fails on an unbound name).
+
+    data_info is the reference's: path_LQ, path_GT, folder, idx ('i/max'), border (1 for the N_frames // 2 frames at either end).
+    The cache holds every clip ONCE as uint8 [T, H, W, C] in cv2's byte order -- a quarter of the reference's f32 cache -- and a sample
+    is {'LQs': uint8 [N, H, W, C] (the window of index_generation), 'GT': uint8 [1, H, W, C], 'folder', 'idx', 'border'}: the batch a
+    DataLoader makes of it goes through the models' feed_data as it is (whole frames, no flags).  clip(folder) hands out a whole cached
+    clip for the clip-wise validation pass of realvsr_amd.train.  Like the other data sets it never touches the device."""
+    NAMES = ('vid4', 'reds4', 'realvsr_test')
+
+    def __init__(self, opt):
+        super(VideoTestDataset, self).__init__()
+        self.opt = opt
+        self.cache_data = opt['cache_data']
+        self.half_N_frames = opt['N_frames'] // 2
+        self.GT_root, self.LQ_root = opt['dataroot_GT'], opt['dataroot_LQ']
+        self.data_type = opt['data_type']
+        self.data_info = {'path_LQ': [], 'path_GT': [], 'folder': [], 'idx': [], 'border': []}
+        if self.data_type == 'lmdb':
+            raise ValueError('No need to use LMDB during validation/test.')
+        if opt['name'].lower() not in self.NAMES:
+            raise ValueError('Not support video test dataset [%s]. Support %s.' % (opt['name'], ', '.join(self.NAMES)))
+        if not self.cache_data:
+            raise NotImplementedError('VideoTestDataset: cache_data has to be true (reading per sample is not built)')
+        _refuse_color_conversion(opt)
+        index_generation(0, 1, opt['N_frames'], opt['padding'])   # (an unknown padding mode fails here, not in a worker)
+        self.imgs_LQ, self.imgs_GT = {}, {}
+        for sub_LQ, sub_GT in zip(self._listing(self.LQ_root), self._listing(self.GT_root)):
+            folder = os.path.basename(sub_GT)
+            paths_LQ, paths_GT = self._listing(sub_LQ), self._listing(sub_GT)
+            max_idx = len(paths_LQ)
+            assert max_idx == len(paths_GT), 'Different number of images in LQ and GT folders'
+            self.data_info['path_LQ'].extend(paths_LQ)
+            self.data_info['path_GT'].extend(paths_GT)
+            self.data_info['folder'].extend([folder] * max_idx)
+            self.data_info['idx'].extend('{}/{}'.format(i, max_idx) for i in range(max_idx))
+            self.data_info['border'].extend(int(i < self.half_N_frames or i >= max_idx - self.half_N_frames) for i in range(max_idx))
+            self.imgs_LQ[folder] = self._read_clip(paths_LQ)
+            self.imgs_GT[folder] = self._read_clip(paths_GT)
+
+    @staticmethod
+    def _listing(root):
+        """sorted(glob(root/*)): the entries in name order, hidden ones left out."""
+        return [os.path.join(root, v) for v in sorted(os.listdir(root)) if not v.startswith('.')]
+
+    @staticmethod
+    def _read_clip(paths):
+        frames = [_read_png_u8(p) for p in paths]
+        frames = [f[:, :, None] if f.ndim == 2 else f[:, :, :3] for f in frames]
+        return torch.from_numpy(np.stack(frames, axis=0))    # (the copy drops the reversed-channel view of _read_png_u8)
+
+    def clip(self, folder):
+        """(LQ uint8 [T, H, W, C], GT uint8 [T, H', W', C]) of one clip: the cached tensors themselves, not copies."""
+        return self.imgs_LQ[folder], self.imgs_GT[folder]
+
+    def folders(self):
+        """The clips in the order their samples come."""
+        return list(self.imgs_GT)
+
+    def __getitem__(self, index):
+        folder = self.data_info['folder'][index]
+        idx, max_idx = (int(v) for v in self.data_info['idx'][index].split('/'))
+        select_idx = index_generation(idx, max_idx, self.opt['N_frames'], padding=self.opt['padding'])
+        return {'LQs': self.imgs_LQ[folder].index_select(0, torch.tensor(select_idx, dtype=torch.long)),
+                'GT': self.imgs_GT[folder][idx:idx + 1], 'folder': folder, 'idx': self.data_info['idx'][index],
+                'border': self.data_info['border'][index]}
+
+    def __len__(self):
+        return len(self.data_info['path_GT'])
+
+
+MAX_WORKERS = 16   # a command gets 16 CPUs whatever the machine has; never sized by os.cpu_count()
+
+
+def create_dataset(dataset_opt):
+    """create_dataset of codes/data/__init__.py:28-49: the data set class that dataset_opt['mode'] names."""
+    import logging
+    modes = {'VideoTest': VideoTestDataset, 'Vimeo90k': Vimeo90kDataset, 'Vimeo90k_AllPair': Vimeo90kAllPairDataset,
+             'RealVSR': RealVSRDataset, 'RealVSR_AllPair': RealVSRAllPairDataset}
+    mode = dataset_opt['mode']
+    if mode not in modes:
+        raise NotImplementedError('Dataset [{:s}] is not recognized.'.format(str(mode)))
+    dataset = modes[mode](dataset_opt)
+    logging.getLogger('base').info('Dataset [{:s} - {:s}] is created.'.format(dataset.__class__.__name__, dataset_opt['name']))
+    return dataset
+
+
+def create_dataloader(dataset, dataset_opt, opt=None, sampler=None):
+    """create_dataloader of codes/data/__init__.py:7-25.  Phase 'train': with opt['dist'] every rank loads batch_size // world samples
+    with n_workers workers and the sampler's order, otherwise batch_size samples, shuffled, with n_workers per entry of gpu_ids;
+    incomplete batches are dropped.  Any other phase: one sample at a time, in order, one worker.  At most MAX_WORKERS workers."""
+    if dataset_opt['phase'] == 'train':
+        if opt['dist']:
+            world_size = torch.distributed.get_world_size()
+            num_workers = dataset_opt['n_workers']
+            assert dataset_opt['batch_size'] % world_size == 0
+            batch_size = dataset_opt['batch_size'] // world_size
+            shuffle = False
+        else:
+            num_workers = dataset_opt['n_workers'] * len(opt['gpu_ids'])
+            batch_size = dataset_opt['batch_size']
+            shuffle = True
+        return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=min(num_workers, MAX_WORKERS),
+                                           sampler=sampler, drop_last=True, pin_memory=False)
+    return torch.utils.data.DataLoader(dataset, batch_size=1, shuffle=False, num_workers=1, pin_memory=True)
+
+
+class DistIterSampler(torch.utils.data.Sampler):
+    """DistIterSampler of codes/data/data_sampler.py: a distributed sampler whose "epoch" is the data set `ratio` times over, so that
+    the loader's workers restart `ratio` times less often.  Every rank draws the same randperm(total_size) from a generator seeded by
+    the epoch (set_epoch), takes it modulo the data-set length and keeps every num_replicas-th entry from its own rank on;
+    total_size = num_replicas * ceil(len(dataset) * ratio / num_replicas)."""
+
+    def __init__(self, dataset, num_replicas=None, rank=None, ratio=100):
+        if num_replicas is None:
+            num_replicas = torch.distributed.get_world_size()
+        if rank is None:
+            rank = torch.distributed.get_rank()
+        self.dataset, self.num_replicas, self.rank, self.epoch = dataset, num_replicas, rank, 0
+        self.num_samples = -(-len(dataset) * ratio // num_replicas)
+        self.total_size = self.num_samples * num_replicas
+
+    def __iter__(self):
+        g = torch.Generator()
+        g.manual_seed(self.epoch)
+        perm = torch.randperm(self.total_size, generator=g)
+        return iter((perm[self.rank::self.num_replicas] % len(self.dataset)).tolist())
+
+    def __len__(self):
+        return self.num_samples
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch

@@ -22,30 +22,9 @@ import ctypes
 import torch
 
 from . import _lib
-from .data import clip_from_u8   # noqa: F401  (read_img_seq for the test scripts: uint8 [T, H, W, C] -> f32 [T, C, H, W] on the device)
+from .data import clip_from_u8, index_generation   # noqa: F401  (read_img_seq for the test scripts: uint8 [T, H, W, C] -> f32 [T, C, H, W] on the
+#                                                     device; index_generation lives with the data sets, which use it on the host)
 from .functional import _need_cuda, _p, _stream
-
-
-def index_generation(crt_i, max_n, N, padding='reflection'):
-    """Indices of the N frames centred on `crt_i` in a sequence of `max_n` frames (counted from 1).
-
-    padding: replicate | reflection | new_info | circle; e.g. crt_i = 0, N = 5:
-    [0, 0, 0, 1, 2] | [2, 1, 0, 1, 2] | [4, 3, 0, 1, 2] | [3, 4, 0, 1, 2]   (codes/data/util.py:169-214)."""
-    last = max_n - 1
-    half = N // 2
-    if padding not in ('replicate', 'reflection', 'new_info', 'circle'):
-        raise ValueError('Wrong padding mode')
-    idx = []
-    for i in range(crt_i - half, crt_i + half + 1):
-        if i < 0:
-            j = {'replicate': 0, 'reflection': -i, 'new_info': crt_i + half - i, 'circle': N + i}[padding]
-        elif i > last:
-            j = {'replicate': last, 'reflection': 2 * last - i, 'new_info': crt_i - half - (i - last),
-                 'circle': i - N}[padding]
-        else:
-            j = i
-        idx.append(j)
-    return idx
 
 
 def single_forward(model, inp):
@@ -99,7 +78,7 @@ class SlidingWindowRunner(object):
         overwrites one slot (the entering frame; at a clip's ends whatever the padding mode changes) instead of gathering the whole
         window, and the window's frame order is a rotation of the ring -- one captured graph per rotation (N graphs, captured on
         first use, sharing one memory pool), replayed round-robin."""
-        if N // 2 != net.center:
+        if N // 2 != getattr(net, 'center', N // 2):   # (TDAN, RCAN, TOF take the middle frame and keep no attribute for it)
             raise RuntimeError('window of %d frames does not match the network centre %d' % (N, net.center))
         self.net, self.N, self.padding, self.chunk, self.flip = net, N, padding, chunk, flip_ensemble
         self.use_graph = use_graph
@@ -193,13 +172,13 @@ class SlidingWindowRunner(object):
         return torch.cat(outs, 0)
 
 
-def evaluate_clip(runner, clip, gt, crop_border=0, ssim=True):
+def evaluate_clip(runner, clip, gt, crop_border=0, ssim=True, keep_output=False):
     """Super-resolve `clip` [T, C, H, W] with a SlidingWindowRunner and score every frame against `gt` [T, C, sH, sW] on the device:
     the per-clip part of codes/test_RealVSR_wi_GT.py:113-168 (channel 0, crop_border, PSNR and SSIM per frame, then the centre / border /
     total averages with border_frame = N // 2, :58).  A runner around a network without `extract_features` (anything but EDVR) goes
     through `reference_order`, one network call per window.  Only the scalars leave the device.
     Returns {'psnr': [T], 'ssim': [T], 'psnr_avg', 'psnr_center', 'psnr_border', 'ssim_avg', 'ssim_center', 'ssim_border'} (the
-    'ssim*' keys only with ssim=True)."""
+    'ssim*' keys only with ssim=True); with keep_output also 'output': the [T, C, sH, sW] frames, still on the device."""
     from . import metrics
     _need_cuda(clip, gt)
     if hasattr(runner.net, 'extract_features'):
@@ -213,4 +192,6 @@ def evaluate_clip(runner, clip, gt, crop_border=0, ssim=True):
     for name in list(res):
         for k, v in metrics.center_border_average(res[name], runner.N // 2).items():
             res['%s_%s' % (name, k)] = v
+    if keep_output:
+        res['output'] = out
     return res
