@@ -294,14 +294,25 @@ class VideoSRGANModel(_TrainingState):
     backward passes: real, fake).  Both optimizers are FlatAdam; every operator is a HIP kernel (discriminator_arch, loss.GANLoss).
     The reference's call order of D -- hence the BatchNorm running statistics -- is kept: 5 forwards per RaGAN step, 3 per vanilla step,
     2 of them skipped on steps without a G update.
-    Out of scope (NotImplementedError): the CPU path, opt['dist'], the VGG feature loss, 'lsgan' / 'wgan-gp'."""
+
+    With ``opt['dist']`` (one process per GPU, the reference's DistributedDataParallel around netG and netD) every rank starts from
+    rank 0's parameters and buffers, and each optimizer's flat gradient buffer has its own dist.BucketedGradAllReduce: G's buckets
+    leave during the G backward (D is frozen there, so only G's hooks fire); D's reducer is armed for two passes and its buckets leave
+    during the second one (l_d_fake.backward()).  Steps without a G update issue no G collective on any rank (the condition depends on
+    `step` alone).  BatchNorm in D normalises with the batch statistics of the rank's own shard, as the reference's plain BatchNorm2d
+    under DDP does (no SyncBN); the running statistics are not exchanged -- D never runs in eval mode, so they never feed back into a
+    step, and rank 0, which writes the checkpoints, saves its own (what the reference's per-forward re-broadcast of rank 0's buffers
+    amounts to, without its traffic).  The logged terms are the local rank's.
+    Out of scope (NotImplementedError): the CPU path, opt['dist'] without a process group, the VGG feature loss, 'lsgan' / 'wgan-gp'."""
 
     def __init__(self, opt):
         self.opt = opt
         if opt.get('gpu_ids', 0) is None or not torch.cuda.is_available():
             raise NotImplementedError('realvsr_amd runs on MI355X only: there is no CPU path (gpu_ids=None)')
-        if opt.get('dist'):
-            raise NotImplementedError('VideoSRGANModel: distributed training (two backward passes over two reducers) is not built')
+        self.dist = bool(opt.get('dist'))
+        if self.dist and not torch.distributed.is_initialized():
+            raise NotImplementedError('VideoSRGANModel: distributed training needs an initialised process group, one process per GPU '
+                                      '(python -m torch.distributed.run ... -m realvsr_amd.train -opt FILE --launcher pytorch)')
         self.is_train = opt['is_train']
         train_opt = opt.get('train') or {}
         if self.is_train:
@@ -312,7 +323,7 @@ class VideoSRGANModel(_TrainingState):
                 raise NotImplementedError('VideoSRGANModel: gan_type %r is not built (gan | ragan)' % (gan_type,))
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.schedulers, self.optimizers = [], []
-        self.rank = -1
+        self.rank = torch.distributed.get_rank() if self.dist else -1
 
         self.netG = networks.define_G(opt).to(self.device)
         self.netD = None
@@ -321,6 +332,11 @@ class VideoSRGANModel(_TrainingState):
             self.netG.train()
             self.netD.train()
         self.load()
+        if self.dist:
+            broadcast_parameters(self.netG)
+            if self.netD is not None:
+                broadcast_parameters(self.netD)
+        self.reducer_G = self.reducer_D = None
         if not self.is_train:
             return
 
@@ -343,6 +359,11 @@ class VideoSRGANModel(_TrainingState):
                                     betas=(train_opt['beta1_D'], train_opt['beta2_D']))
         self.optimizers.append(self.optimizer_D)
         self._build_schedulers(train_opt, 'MultiStepLR')
+        if self.dist:
+            bucket_mb = float(os.environ.get('RVSR_BUCKET_MB', train_opt.get('bucket_mb', 4.0)))
+            force = bool(train_opt.get('force_allreduce'))
+            self.reducer_G = BucketedGradAllReduce(None, bucket_mb=bucket_mb, buffers=self.optimizer_G.buffers, broadcast=False, force=force)
+            self.reducer_D = BucketedGradAllReduce(None, bucket_mb=bucket_mb, buffers=self.optimizer_D.buffers, broadcast=False, force=force)
         self.log_dict = OrderedDict()
 
     # ------------------------------------------------------------------ data
@@ -367,7 +388,10 @@ class VideoSRGANModel(_TrainingState):
         from . import util
         # G
         self._set_requires_grad_D(False)
-        self.optimizer_G.zero_grad()
+        if self.reducer_G is not None:
+            self.reducer_G.zero_grad()
+        else:
+            self.optimizer_G.zero_grad()
         aug = self.opt.get('augment')
         if aug:
             self.var_H, self.var_L = augments.apply_augment(self.var_H, self.var_L, aug['augs'], aug['probs'], aug['alphas'], aug['mix_p'])
@@ -410,11 +434,16 @@ class VideoSRGANModel(_TrainingState):
             total = total + l_g_gan
             terms['l_g_total'] = total
             total.backward()
+            if self.reducer_G is not None:
+                self.reducer_G.finish()
             self.optimizer_G.step()
 
         # D
         self._set_requires_grad_D(True)
-        self.optimizer_D.zero_grad()
+        if self.reducer_D is not None:
+            self.reducer_D.zero_grad(passes=2)
+        else:
+            self.optimizer_D.zero_grad()
         fake_in = [x.detach() for x in fake_pyr[:-1]]
         real_in = ref_pyr[:-1]
         l_d_real, l_d_fake = 0, 0
@@ -438,6 +467,8 @@ class VideoSRGANModel(_TrainingState):
             for i in range(len(pred_d_fake)):
                 l_d_fake = l_d_fake + self.cri_gan(pred_d_fake[i], False)
             l_d_fake.backward()
+        if self.reducer_D is not None:
+            self.reducer_D.finish()
         self.optimizer_D.step()
         terms['l_d_real'] = l_d_real.detach()
         terms['l_d_fake'] = l_d_fake.detach()

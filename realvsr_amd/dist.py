@@ -91,9 +91,23 @@ class BucketedGradAllReduce:
         torch.cuda.synchronize()
         return sum(a.elapsed_time(b) for a, b in self._exposed) / len(self._exposed)
 
-    def zero_grad(self):
+    @property
+    def issued(self):
+        """Buckets whose all-reduce has been enqueued since the last zero_grad."""
+        return self._next
+
+    def zero_grad(self, passes=1):
+        """Start a step whose gradients are accumulated over `passes` backward passes into the flat buffer (the GAN stage's D step:
+        l_d_real.backward(), then l_d_fake.backward()).  A bucket is ready once every one of its parameters has delivered `passes`
+        gradients, and no collective is issued before that: a bucket that left after the first pass would have the second pass add
+        local gradients on top of a sum that was already reduced.  So overlap exists only in the FINAL pass -- the earlier passes run
+        without any traffic -- and `stats_issued_in_backward` counts the buckets that left during it.  A parameter that receives a
+        gradient in fewer passes than announced (or in none) keeps its bucket back until finish(), which flushes it like any bucket
+        that did not arrive.  passes=1 is the single-backward step."""
+        if passes < 1:
+            raise ValueError('BucketedGradAllReduce.zero_grad: passes must be >= 1')
         self.buffers.zero_grad()
-        self._pending = list(self._need)
+        self._pending = list(self._need) if passes == 1 else [n * passes for n in self._need]
         self._next = 0
         self._works = []
 

@@ -1,6 +1,6 @@
 """Train from a reference option file:
 
-    python -m realvsr_amd.train -opt FILE [--launcher none|pytorch] [--root DIR] [--model NAME]
+    python -m realvsr_amd.train -opt FILE [--launcher none|pytorch] [--dist-backend nccl|gloo] [--root DIR] [--model NAME]
 
 The loop of codes/train.py in the same order -- schedule, data, step, log line, validation, checkpoint -- around the models of
 realvsr_amd.VideoSR_model, whose step is the HIP hot path.  What differs from the reference is where the work happens, not what is done:
@@ -14,7 +14,10 @@ realvsr_amd.VideoSR_model, whose step is the HIP hot path.  What differs from th
     create_model knows (e.g. --model VideoSR_AllPair_YCbCr_Combine).
 
 Distributed runs are started from outside, one process per GPU: python -m torch.distributed.run --nproc_per_node=K -m realvsr_amd.train
--opt FILE --launcher pytorch.  This module never starts or replaces a process itself.
+-opt FILE --launcher pytorch, for the PSNR models and the GAN model alike (the models broadcast rank 0's networks and all-reduce the
+gradients; every rank resumes both optimizers from the .state file; rank 0 alone logs, validates and saves).  --dist-backend gloo lets a
+one-GPU box rehearse that driver with all ranks on the same device (RCCL does not accept two ranks on one device); RVSR_DIST_CHECK=1 makes
+every rank log a checksum of its flat parameter buffers at the end of the run.  This module never starts or replaces a process itself.
 """
 import argparse
 import logging
@@ -106,8 +109,8 @@ def validate(model, val_set, step, logger=None, tb_logger=None, save_images=True
     the encoder runs on the host while the device waits).  netG is in eval() during the pass and in train() afterwards.
     A folder's mean is sum(v) / len(v), the total the mean of the folders' means.
 
-    With opt['dist'] the caller (train below) has rank 0 validate while the other ranks wait at a barrier; that multi-rank path has not
-    been run (it needs more than one GPU).
+    With opt['dist'] the caller (train below) has rank 0 validate while the other ranks wait at a barrier (run with two gloo ranks sharing
+    one GPU, tests/test_gpu_gan_dist.py; never on several GPUs: a pass longer than the process group's timeout would end the run there).
 
     Returns {'psnr': {folder: [per frame]}, 'psnr_avg': {folder: mean}, 'psnr_total': mean of means}."""
     from PIL import Image
@@ -215,6 +218,10 @@ def train(opt, model, train_loader, val_set=None, train_sampler=None, resume_sta
                 model.save(current_step)
                 model.save_training_state(epoch, current_step)
 
+    if opt.get('dist') and os.environ.get('RVSR_DIST_CHECK', '0') == '1':
+        # developer check: every rank's line must carry the same numbers (the sum of the parameters' bit patterns, per optimizer)
+        sums = [int(o.buffers.param.view(torch.int32).sum(dtype=torch.int64)) for o in model.optimizers]
+        logger.info('rank {:d}: iter {:d}, parameter checksums {}'.format(rank, current_step, ' '.join(str(v) for v in sums)))
     if rank <= 0:
         logger.info('Saving the final model.')
         model.save('latest')
@@ -226,6 +233,8 @@ def main(argv=None):
     parser = argparse.ArgumentParser(prog='python -m realvsr_amd.train', description=__doc__.split('\n\n')[0])
     parser.add_argument('-opt', type=str, required=True, help='path to the option YAML file')
     parser.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='pytorch: started by torch.distributed.run')
+    parser.add_argument('--dist-backend', choices=['nccl', 'gloo'], default='nccl',
+                        help='pytorch launcher: nccl = RCCL, one GPU per rank; gloo = rehearsal with all ranks on one GPU')
     parser.add_argument('--local_rank', type=int, default=0)
     parser.add_argument('--root', type=str, default=None, help='where experiments/<name> goes (default: the current directory)')
     parser.add_argument('--model', type=str, default=None, help="replaces the option file's `model`")
@@ -243,7 +252,7 @@ def main(argv=None):
         rank = -1
     else:
         opt['dist'] = True
-        init_dist()
+        init_dist(backend=args.dist_backend)
         world_size = torch.distributed.get_world_size()
         rank = torch.distributed.get_rank()
 
