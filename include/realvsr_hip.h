@@ -706,6 +706,30 @@ int rvsr_assemble_clips(const unsigned char* src, float* dst, const int* flags, 
 int rvsr_assemble_plan(const float* dst, size_t samples, int frames, int C, int Hs, int Ws, RVSR_HOST int* variant, RVSR_HOST int* blocks);
 
 /* ---------------------------------------------------------------------------------------------
+ * 12b. Batch assembly from a resident frame store (codes/data/RealVSR_dataset.py:120-172, 283-341, codes/data/util.py:86-101, 261-276)
+ * --------------------------------------------------------------------------------------------- */
+
+/* The same float32 batch as rvsr_assemble_clips, gathered from whole decoded frames that stay on the device: what the reference does
+ * per sample with read_img on every frame of the window (RealVSR_dataset.py:120-140, 283-307: cv2.imread of a 1024 x 512 file each), the
+ * crop (:154-157, :321-324), util.augment (:160-163, :327-330) and the stack / [2, 1, 0] / CHW tail (:166-172, :333-341) -- with the
+ * files decoded once, at start-up.
+ *   store  uint8 [store_frames][H][W][C], contiguous, at ANY byte alignment; read like `src` above (16-byte loads aligned down, none
+ *          from an aligned block that holds no byte of a crop); every byte offset into it is a size_t
+ *   table  int32 [samples][frames + 3] (device memory): per sample `frames` store slots, then the crop's row, its column, and the flags
+ *          of section 12 (bits 0-2; higher bits are ignored)
+ *   dst    float32 [samples][frames][C][S][S], fully overwritten, nothing outside it written:
+ *              dst[b][f] = assemble(store[slot[b][f]][row_b : row_b + S, col_b : col_b + S], flags_b, mode)
+ *          bit for bit the values of rvsr_assemble_clips on those crops packed contiguously (the kernels share the tile body)
+ *   C      1 or 3;  1 <= S <= min(H, W) (RVSR_ERR_BAD_ARG otherwise);  mode as in section 12
+ * What the table holds is device data the entry point cannot see: the kernel clamps a slot into [0, store_frames) and the origin into
+ * [0, H - S] x [0, W - S], so a wrong table gives wrong pixels, never an access outside the store. */
+int rvsr_gather_clips(const unsigned char* store, size_t store_frames, int H, int W, const int* table, float* dst, size_t samples,
+                      int frames, int C, int S, int mode, void* stream);
+/* The plan of that call (pure host code; the same shape checks where it has the numbers): *variant = 1 for 16-byte stores (S % 4 == 0
+ * and dst 16-byte aligned), 0 for scalar stores; *blocks = workgroups (one per 64 x 64 output tile of an image). */
+int rvsr_gather_plan(const float* dst, size_t samples, int frames, int C, int S, RVSR_HOST int* variant, RVSR_HOST int* blocks);
+
+/* ---------------------------------------------------------------------------------------------
  * 13. Bicubic degradation of uint8 frames (codes/scripts/generate_LR_BI_Vimeo90K.m:28, codes/data/util.py:511-710)
  * --------------------------------------------------------------------------------------------- */
 

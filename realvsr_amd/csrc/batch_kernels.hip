@@ -16,6 +16,8 @@
 // allocation) cannot fault; those bytes reach LDS and are never read back.  Every store goes to an element of `dst` the tile owns.
 // The read-out walks the OUTPUT row-major (four consecutive x per thread, 16-byte stores where Wo % 4 == 0), so both global sides are
 // coalesced whatever the flags say; the transposition of rot90 happens in the LDS byte reads.
+// rvsr_gather_clips is the same tile read from where the crop still sits in its whole frame: a data set decoded once into a resident
+// store u8 [store_frames][H][W][C], and per sample a table row of store slots, crop origin and flags (gather_kernel below).
 #include "glue_common.h"
 
 // (a native vector type: an array of HIP's uint4 struct is not promoted to registers and leaves dead stores to scratch behind)
@@ -34,17 +36,17 @@ __device__ __forceinline__ int div255000_rhe(int v) {
     return q;
 }
 
+// The body both kernels share: one 64 x 64 tile of one Hs x Ws output image.  `origin` is the byte of source pixel (0, 0) of the image's
+// Hs x Ws source rectangle and `row_bytes` the distance between two of its rows -- Ws * C for packed crops, the FRAME's W * C for a crop
+// that still sits in its frame (gather_kernel).  Nothing else knows where the source is; the RULE above holds for any pitch, because the
+// blocks a row loads are found from that row's own first and last byte.
 template <int C, bool VEC>
-__global__ void __launch_bounds__(256) assemble_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst,
-                                                       const int* __restrict__ flags, int frames, int Hs, int Ws, int mode,
-                                                       unsigned tiles_x, unsigned tiles) {
+__device__ __forceinline__ void assemble_tile(const unsigned char* __restrict__ origin, size_t row_bytes, float* __restrict__ out, int f,
+                                              int Hs, int Ws, int mode, unsigned tile, unsigned tiles_x) {
     __shared__ asm_u32x4 stage4[ASM_T * ASM_BLK];
     __shared__ float tab[256];
     const unsigned char* stage = (const unsigned char*)stage4;
     const int tid = threadIdx.x;
-    const size_t image = blockIdx.x / tiles;
-    const unsigned tile = blockIdx.x - (unsigned)image * tiles;
-    const int f = flags ? flags[image / (size_t)frames] : 0;   // (uniform)
     const bool hf = f & 1, vf = f & 2, rot = f & 4;
     const int Ho = Hs, Wo = Ws;   // (rot90 needs Hs == Ws: checked by the entry point)
     const int Y0 = (int)(tile / tiles_x) * ASM_T, X0 = (int)(tile % tiles_x) * ASM_T;
@@ -53,9 +55,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const unsigned char* __re
     const int AY0 = rot ? X0 : Y0, AY1 = rot ? X1 : Y1, AX0 = rot ? Y0 : X0, AX1 = rot ? Y1 : X1;
     const int SY0 = vf ? Hs - AY1 : AY0, SX0 = hf ? Ws - AX1 : AX0;
     const int nr = AY1 - AY0, len = (AX1 - AX0) * C;   // rows of the rectangle, bytes per row: 1 .. 64, 1 .. 192
-    const unsigned char* img = src + image * (size_t)Hs * Ws * C;
-    const size_t row_bytes = (size_t)Ws * C;
-    const unsigned char* rect = img + (size_t)SY0 * row_bytes + (size_t)SX0 * C;
+    const unsigned char* rect = origin + (size_t)SY0 * row_bytes + (size_t)SX0 * C;
 
     tab[tid] = __fdiv_rn((float)tid, 255.f);
 
@@ -80,7 +80,6 @@ __global__ void __launch_bounds__(256) assemble_kernel(const unsigned char* __re
 
     const unsigned head0 = (unsigned)((uintptr_t)rect & 15), head_step = (unsigned)(row_bytes & 15);
     const size_t plane = (size_t)Ho * Wo;
-    float* out = dst + image * C * plane;
     const bool rev = mode & 1, ycc = C == 3 && (mode & 2);
 #pragma unroll
     for (int it = 0; it < ASM_T * ASM_T / 4 / 256; ++it) {
@@ -117,6 +116,36 @@ __global__ void __launch_bounds__(256) assemble_kernel(const unsigned char* __re
             }
         }
     }
+}
+
+template <int C, bool VEC>
+__global__ void __launch_bounds__(256) assemble_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst,
+                                                       const int* __restrict__ flags, int frames, int Hs, int Ws, int mode,
+                                                       unsigned tiles_x, unsigned tiles) {
+    const size_t image = blockIdx.x / tiles;
+    const unsigned tile = blockIdx.x - (unsigned)image * tiles;
+    const int f = flags ? flags[image / (size_t)frames] : 0;   // (uniform)
+    const size_t row_bytes = (size_t)Ws * C;
+    assemble_tile<C, VEC>(src + image * (size_t)Hs * row_bytes, row_bytes, dst + image * C * ((size_t)Hs * Ws), f, Hs, Ws, mode, tile,
+                          tiles_x);
+}
+
+// The same tiles read out of a resident store u8 [store_frames][H][W][C]: row b of `table` (frames + 3 ints) names the store slot of
+// every frame of sample b, then the crop's row, its column and the flags.  Slot and origin are CLAMPED into the store, so a wrong table
+// gives wrong pixels, never a read outside it; every byte offset is a size_t (a store is tens of gigabytes).
+template <int C, bool VEC>
+__global__ void __launch_bounds__(256) gather_kernel(const unsigned char* __restrict__ store, float* __restrict__ dst,
+                                                     const int* __restrict__ table, int frames, int store_frames, int H, int W, int S,
+                                                     int mode, unsigned tiles_x, unsigned tiles) {
+    const size_t image = blockIdx.x / tiles;
+    const unsigned tile = blockIdx.x - (unsigned)image * tiles;
+    const size_t b = image / (size_t)frames;
+    const int* row = table + b * (size_t)(frames + 3);   // (uniform)
+    const int slot = min(max(row[image - b * (size_t)frames], 0), store_frames - 1);
+    const int y0 = min(max(row[frames], 0), H - S), x0 = min(max(row[frames + 1], 0), W - S);
+    const size_t row_bytes = (size_t)W * C;
+    const unsigned char* origin = store + ((size_t)slot * (size_t)H + (size_t)y0) * row_bytes + (size_t)x0 * C;
+    assemble_tile<C, VEC>(origin, row_bytes, dst + image * C * ((size_t)S * S), row[frames + 2] & 7, S, S, mode, tile, tiles_x);
 }
 
 // ---------------------------------------------------------------- host side
@@ -166,4 +195,52 @@ extern "C" int rvsr_assemble_clips(const unsigned char* src, float* dst, const i
     else ASM_LAUNCH(1, false);
 #undef ASM_LAUNCH
     RETURN_LAUNCH("assemble_clips");
+}
+
+// (the plan has neither store nor table and passes dst in their place, as rvsr_assemble_plan does for src)
+static int gather_args(const void* store, const void* table, const void* dst, size_t store_frames, int H, int W, size_t samples,
+                       int frames, int C, int S, int mode, size_t* blocks) {
+    if (!store || !table || !dst) FAIL(RVSR_ERR_BAD_ARG, "gather_clips: null argument");
+    if (samples == 0 || frames <= 0 || store_frames == 0 || H <= 0 || W <= 0)
+        FAIL(RVSR_ERR_BAD_ARG, "gather_clips: empty shape (%zu samples, %d frames, a store of %zu frames of %d x %d)", samples, frames,
+             store_frames, H, W);
+    if (store_frames > 0x7fffffffu) FAIL(RVSR_ERR_UNSUPPORTED, "gather_clips: %zu store frames (a slot is an int32)", store_frames);
+    if (((uintptr_t)dst & 3) != 0) FAIL(RVSR_ERR_BAD_ARG, "gather_clips: dst is not aligned to its float32 elements");
+    if (((uintptr_t)table & 3) != 0) FAIL(RVSR_ERR_BAD_ARG, "gather_clips: the table is not aligned to its int32 elements");
+    if (C != 1 && C != 3) FAIL(RVSR_ERR_UNSUPPORTED, "gather_clips: %d channels (1 or 3)", C);
+    if (S < 1 || S > H || S > W) FAIL(RVSR_ERR_BAD_ARG, "gather_clips: a crop of %d leaves the %d x %d frame", S, H, W);
+    if (mode & ~(RVSR_ASM_REVERSE | RVSR_ASM_TO_YCBCR)) FAIL(RVSR_ERR_UNSUPPORTED, "gather_clips: mode %d", mode);
+    if ((mode & RVSR_ASM_TO_YCBCR) && C != 3) FAIL(RVSR_ERR_UNSUPPORTED, "gather_clips: the YCbCr conversion needs 3 channels");
+    const size_t tiles = (size_t)((S + ASM_T - 1) / ASM_T) * (size_t)((S + ASM_T - 1) / ASM_T);
+    if (tiles > 0x7fffffffu || samples * (size_t)frames > 0x7fffffffu / tiles)
+        FAIL(RVSR_ERR_UNSUPPORTED, "gather_clips: %zu images of %zu tiles exceed one launch", samples * (size_t)frames, tiles);
+    *blocks = samples * (size_t)frames * tiles;
+    return RVSR_OK;
+}
+
+extern "C" int rvsr_gather_plan(const float* dst, size_t samples, int frames, int C, int S, int* variant, int* blocks) {
+    size_t nb = 0;
+    const int rc = gather_args(dst, dst, dst, 1, S, S, samples, frames, C, S, 0, &nb);
+    if (rc != RVSR_OK) return rc;
+    if (variant) *variant = assemble_variant(dst, S);
+    if (blocks) *blocks = (int)nb;
+    return RVSR_OK;
+}
+
+extern "C" int rvsr_gather_clips(const unsigned char* store, size_t store_frames, int H, int W, const int* table, float* dst,
+                                 size_t samples, int frames, int C, int S, int mode, void* stream) {
+    size_t nb = 0;
+    const int rc = gather_args(store, table, dst, store_frames, H, W, samples, frames, C, S, mode, &nb);
+    if (rc != RVSR_OK) return rc;
+    const unsigned tiles_x = (unsigned)((S + ASM_T - 1) / ASM_T), tiles = tiles_x * tiles_x;
+    const int variant = assemble_variant(dst, S);
+#define GAT_LAUNCH(CC, VV)                                                                                                          \
+    hipLaunchKernelGGL((gather_kernel<CC, VV>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, store, dst, table, frames, \
+                       (int)store_frames, H, W, S, mode, tiles_x, tiles)
+    if (C == 3 && variant) GAT_LAUNCH(3, true);
+    else if (C == 3) GAT_LAUNCH(3, false);
+    else if (variant) GAT_LAUNCH(1, true);
+    else GAT_LAUNCH(1, false);
+#undef GAT_LAUNCH
+    RETURN_LAUNCH("gather_clips");
 }

@@ -9,6 +9,8 @@ realvsr_amd.VideoSR_model, whose step is the HIP hot path.  What differs from th
     device); the learning rate is host arithmetic that reaches the optimizer kernel as an argument;
   * validation runs clip by clip on the device (validate below): a clip is uploaded once as uint8, every frame's features are computed
     once (infer.SlidingWindowRunner) and only the per-frame PSNR scalars and every fifth frame's 3 bytes per pixel come back;
+  * a RealVSR train data set with `resident: true` is decoded once into device memory and its batches are gathered there
+    (realvsr_amd.resident: the same samples in the same order as the file loader with n_workers 0; resident_max_gb is the budget);
   * experiments go under --root (default: the current directory), CUDA_VISIBLE_DEVICES is left alone (realvsr_amd.options);
   * --model replaces the option file's `model` before create_model: the six Vimeo-90K files name 'VideoSR_AllPair', which no
     create_model knows (e.g. --model VideoSR_AllPair_YCbCr_Combine).
@@ -294,7 +296,11 @@ def main(argv=None):
             if opt['dist']:
                 train_sampler = DistIterSampler(train_set, world_size, rank, DATASET_RATIO)
                 total_epochs = int(math.ceil(total_iters / (train_size * DATASET_RATIO)))
-            train_loader = create_dataloader(train_set, dataset_opt, opt, train_sampler)
+            if dataset_opt.get('resident'):   # (a key of ours: every frame decoded once into HBM, batches gathered on the device)
+                from .resident import create_resident_loader
+                train_loader = create_resident_loader(train_set, dataset_opt, opt, train_sampler)
+            else:
+                train_loader = create_dataloader(train_set, dataset_opt, opt, train_sampler)
             if rank <= 0:
                 logger.info('Number of train images: {:,d}, iters: {:,d}'.format(len(train_set), train_size))
                 logger.info('Total epochs needed: {:d} for iters {:,d}'.format(total_epochs, total_iters))
