@@ -14,7 +14,8 @@ MI355X wiring instead of DataParallel / DistributedDataParallel + torch.optim.Ad
     all-reduced in buckets over RCCL while backward is still running (dist.BucketedGradAllReduce);
   * augmentation runs as one kernel on the device-resident clip pair (augment.apply_augment).
 The learning-rate schedule, checkpoints and resume of codes/models/base_model.py:38-67, 121-141 are ``_TrainingState`` below, shared by
-both model classes; realvsr_amd.train is the loop that calls them.  Out of scope: the VGG feature loss.
+both model classes through ``_VideoSRBase``, which holds everything else the two have in common; realvsr_amd.train is the loop that
+calls them.  Out of scope: the VGG feature loss.
 ``VideoSRGANModel`` below is the GAN stage (VideoSRGAN_AllPair_model_YCbCr_Split.py) on the same machinery.
 """
 import os
@@ -120,17 +121,126 @@ class _TrainingState:
             self.schedulers[i].load_state_dict(s)
 
 
-class VideoSRModel(_TrainingState):
-    def __init__(self, opt, split=True):
-        self.opt = opt
-        self.split = split
+def _is_packed(data):
+    """Packed crops of realvsr_amd.data: the f32 batch is assembled on the device."""
+    return 'GT_window' in data or data['LQs'].dtype == torch.uint8
+
+
+class _VideoSRBase(_TrainingState):
+    """What the two model classes share beyond the schedules and checkpoints: the set-up around their own refusals, the methods
+    realvsr_amd.train calls on either of them, and the parts of a step that do not depend on its losses."""
+
+    def __init__(self, opt):
         if opt.get('gpu_ids', 0) is None or not torch.cuda.is_available():
             raise NotImplementedError('realvsr_amd runs on MI355X only: there is no CPU path (gpu_ids=None)')
-        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.opt = opt
         self.is_train = opt['is_train']
-        self.schedulers, self.optimizers = [], []
         self.dist = bool(opt.get('dist'))
+
+    def _init_device_state(self):
+        """The first device call of a constructor: after every refusal that reads only the options."""
+        self.device = torch.device('cuda', torch.cuda.current_device())
         self.rank = torch.distributed.get_rank() if self.dist else -1
+        self.schedulers, self.optimizers = [], []
+        self.log_dict = OrderedDict()
+
+    def _build_reducer(self, buffers):
+        """The bucketed all-reduce over one optimizer's flat gradient buffer (the parameters were broadcast when the network was built)."""
+        train_opt = self.opt['train']
+        return BucketedGradAllReduce(None, bucket_mb=float(os.environ.get('RVSR_BUCKET_MB', train_opt.get('bucket_mb', 4.0))),
+                                     buffers=buffers, broadcast=False, force=bool(train_opt.get('force_allreduce')))
+
+    # ------------------------------------------------------------------ data
+    def feed_data(self, data, need_GT=True):
+        if _is_packed(data):
+            self.var_L, var_H = feed_packed(data, self.device, need_GT)
+            if need_GT:
+                self.var_H = var_H
+            return
+        self.var_L = data['LQs'].to(self.device)
+        if need_GT:
+            self.var_H = data['GT'].to(self.device)
+
+    def _center_frame(self, clip):
+        """[B, N, C, H, W] -> the centre frame, N being var_L's; a tensor that holds the centre frame only as is."""
+        return clip[:, self.var_L.size(1) // 2] if clip.dim() == 5 else clip
+
+    # ------------------------------------------------------------------ the parts of a step both models have
+    @staticmethod
+    def _zero_grad(optimizer, reducer, passes=1):
+        if reducer is not None:
+            reducer.zero_grad(passes=passes)
+        else:
+            optimizer.zero_grad()
+
+    @staticmethod
+    def _finish_and_step(optimizer, reducer):
+        if reducer is not None:
+            reducer.finish()
+        optimizer.step()
+
+    def _augment(self):
+        aug = self.opt.get('augment')
+        if aug:
+            self.var_H, self.var_L = augments.apply_augment(self.var_H, self.var_L, aug['augs'], aug['probs'],
+                                                            aug['alphas'], aug['mix_p'])
+
+    def _keep_terms(self, terms, log):
+        self.loss_terms = terms
+        if log:
+            for k, v in terms.items():
+                self.log_dict[k] = v.item()
+
+    def test(self):
+        self.netG.eval()
+        with torch.no_grad():
+            self.fake_H = self.netG(self.var_L)
+        self.netG.train()
+
+    # ------------------------------------------------------------------ bookkeeping
+    def get_current_log(self):
+        return self.log_dict
+
+    def get_current_visuals(self, need_GT=True):
+        out = OrderedDict()
+        out['LQs'] = self.var_L.detach()[0].float().cpu()
+        out['HQ'] = self.fake_H.detach()[0].float().cpu()
+        if need_GT:
+            out['GT'] = self.var_H.detach()[0].float().cpu()
+        return out
+
+    def get_current_metrics(self, ssim=False, crop_border=0):
+        """After feed_data + test(): {'psnr': [per sample], 'ssim': [per sample]} of fake_H against the GT (the centre frame of a
+        five-dimensional var_H) on channel 0 -- the numbers the validation loop of codes/train.py:285-305 gets out of
+        get_current_visuals + tensor2img + calculate_psnr, computed on the device (realvsr_amd.metrics): only the scalars come back."""
+        from . import metrics
+        gt = self._center_frame(self.var_H)
+        res = metrics.frame_metrics(self.fake_H.detach(), gt.detach(), crop_border=crop_border, ssim=ssim)
+        res.setdefault('ssim', [])
+        return res
+
+    def get_current_learning_rate(self):
+        return [g['lr'] for g in self.optimizers[0].param_groups]
+
+    def load(self):
+        path = self.opt.get('path') or {}
+        if path.get('pretrain_model_G') is not None:
+            self.load_network(path['pretrain_model_G'], self.netG, path.get('strict_load', True))
+
+    def load_network(self, load_path, network, strict=True):
+        sd = torch.load(load_path, map_location='cpu')
+        network.load_state_dict(OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items()),
+                                strict=strict)
+
+    def save_network(self, network, save_path):
+        torch.save(OrderedDict((k, v.cpu()) for k, v in network.state_dict().items()), save_path)
+
+
+class VideoSRModel(_VideoSRBase):
+    def __init__(self, opt, split=True):
+        super().__init__(opt)
+        self.split = split
+        self._init_device_state()
         train_opt = opt.get('train') or {}
 
         self.netG = networks.define_G(opt).to(self.device)
@@ -168,21 +278,7 @@ class VideoSRModel(_TrainingState):
         self.optimizers.append(self.optimizer_G)
         self._build_schedulers(train_opt, 'MultiStepLR_Restart')
         if self.dist:
-            self.reducer = BucketedGradAllReduce(None, bucket_mb=float(os.environ.get('RVSR_BUCKET_MB', train_opt.get('bucket_mb', 4.0))),
-                                                 buffers=self.optimizer_G.buffers, broadcast=False,
-                                                 force=bool(train_opt.get('force_allreduce')))
-        self.log_dict = OrderedDict()
-
-    # ------------------------------------------------------------------ data
-    def feed_data(self, data, need_GT=True):
-        if 'GT_window' in data or data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data: the f32 batch is assembled on the device
-            self.var_L, var_H = feed_packed(data, self.device, need_GT)
-            if need_GT:
-                self.var_H = var_H
-            return
-        self.var_L = data['LQs'].to(self.device)
-        if need_GT:
-            self.var_H = data['GT'].to(self.device)
+            self.reducer = self._build_reducer(self.optimizer_G.buffers)
 
     # ------------------------------------------------------------------ one optimisation step
     def set_params_lr_zero(self):
@@ -191,8 +287,7 @@ class VideoSRModel(_TrainingState):
     def forward_loss(self):
         """netG forward + the weighted criteria; returns (total, OrderedDict of the named terms) as device scalars."""
         self.fake_H = self.netG(self.var_L)
-        center_idx = self.var_L.size(1) // 2
-        gt = self.var_H[:, center_idx] if self.var_H.dim() == 5 else self.var_H   # [B, N, C, H, W] (or centre frame only)
+        gt = self._center_frame(self.var_H)
         terms = OrderedDict()
         if self.split:
             terms['l_pix_y'] = self.l_pix_w_y * self.cri_pix_y(self.fake_H[:, 0:1], gt[:, 0:1])
@@ -213,67 +308,12 @@ class VideoSRModel(_TrainingState):
         train_opt = self.opt['train']
         if train_opt.get('ft_tsa_only') and step < train_opt['ft_tsa_only']:
             self.set_params_lr_zero()
-        if self.reducer is not None:
-            self.reducer.zero_grad()
-        else:
-            self.optimizer_G.zero_grad()
-        aug = self.opt.get('augment')
-        if aug:
-            self.var_H, self.var_L = augments.apply_augment(self.var_H, self.var_L, aug['augs'], aug['probs'],
-                                                            aug['alphas'], aug['mix_p'])
+        self._zero_grad(self.optimizer_G, self.reducer)
+        self._augment()
         total, terms = self.forward_loss()
         total.backward()
-        if self.reducer is not None:
-            self.reducer.finish()
-        self.optimizer_G.step()
-        self.loss_terms = terms
-        if log:
-            for k, v in terms.items():
-                self.log_dict[k] = v.item()
-
-    def test(self):
-        self.netG.eval()
-        with torch.no_grad():
-            self.fake_H = self.netG(self.var_L)
-        self.netG.train()
-
-    # ------------------------------------------------------------------ bookkeeping
-    def get_current_log(self):
-        return self.log_dict
-
-    def get_current_visuals(self, need_GT=True):
-        out = OrderedDict()
-        out['LQs'] = self.var_L.detach()[0].float().cpu()
-        out['HQ'] = self.fake_H.detach()[0].float().cpu()
-        if need_GT:
-            out['GT'] = self.var_H.detach()[0].float().cpu()
-        return out
-
-    def get_current_metrics(self, ssim=False, crop_border=0):
-        """After feed_data + test(): {'psnr': [per sample], 'ssim': [per sample]} of fake_H against the GT (the centre frame of a
-        five-dimensional var_H) on channel 0 -- the numbers the validation loop of codes/train.py:285-305 gets out of
-        get_current_visuals + tensor2img + calculate_psnr, computed on the device (realvsr_amd.metrics): only the scalars come back."""
-        from . import metrics
-        gt = self.var_H[:, self.var_L.size(1) // 2] if self.var_H.dim() == 5 else self.var_H
-        res = metrics.frame_metrics(self.fake_H.detach(), gt.detach(), crop_border=crop_border, ssim=ssim)
-        res.setdefault('ssim', [])
-        return res
-
-    def get_current_learning_rate(self):
-        return [g['lr'] for g in self.optimizers[0].param_groups]
-
-    def load(self):
-        path = (self.opt.get('path') or {}).get('pretrain_model_G')
-        if path is not None:
-            self.load_network(path, self.netG, self.opt['path'].get('strict_load', True))
-
-    def load_network(self, load_path, network, strict=True):
-        sd = torch.load(load_path, map_location='cpu')
-        network.load_state_dict(OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items()),
-                                strict=strict)
-
-    def save_network(self, network, save_path):
-        torch.save(OrderedDict((k, v.cpu()) for k, v in network.state_dict().items()), save_path)
+        self._finish_and_step(self.optimizer_G, self.reducer)
+        self._keep_terms(terms, log)
 
 
 def _gan_pixel_criterion(name, channels):
@@ -287,7 +327,7 @@ def _gan_pixel_criterion(name, channels):
     raise NotImplementedError('Loss type [{:s}] is not recognized.'.format(str(name)))
 
 
-class VideoSRGANModel(_TrainingState):
+class VideoSRGANModel(_VideoSRBase):
     """``VideoSRGANModel`` of codes/models/VideoSRGAN_AllPair_model_YCbCr_Split.py (:23-183 constructor, :185-191 feed_data, :193-317
     optimize_parameters): G = the generator of define_G, D = define_D's patch discriminator on the two high-frequency Laplacian bands
     of Y; pixel terms on the pyramid (SSIM / Charbonnier on the bands, GWLoss on CbCr) + the ('ra')GAN term, then the D step (two
@@ -306,14 +346,10 @@ class VideoSRGANModel(_TrainingState):
     Out of scope (NotImplementedError): the CPU path, opt['dist'] without a process group, the VGG feature loss, 'lsgan' / 'wgan-gp'."""
 
     def __init__(self, opt):
-        self.opt = opt
-        if opt.get('gpu_ids', 0) is None or not torch.cuda.is_available():
-            raise NotImplementedError('realvsr_amd runs on MI355X only: there is no CPU path (gpu_ids=None)')
-        self.dist = bool(opt.get('dist'))
+        super().__init__(opt)
         if self.dist and not torch.distributed.is_initialized():
             raise NotImplementedError('VideoSRGANModel: distributed training needs an initialised process group, one process per GPU '
                                       '(python -m torch.distributed.run ... -m realvsr_amd.train -opt FILE --launcher pytorch)')
-        self.is_train = opt['is_train']
         train_opt = opt.get('train') or {}
         if self.is_train:
             if (train_opt.get('feature_weight') or 0) > 0:
@@ -321,9 +357,7 @@ class VideoSRGANModel(_TrainingState):
             gan_type = train_opt['gan_type']
             if gan_type not in ('gan', 'ragan'):
                 raise NotImplementedError('VideoSRGANModel: gan_type %r is not built (gan | ragan)' % (gan_type,))
-        self.device = torch.device('cuda', torch.cuda.current_device())
-        self.schedulers, self.optimizers = [], []
-        self.rank = torch.distributed.get_rank() if self.dist else -1
+        self._init_device_state()
 
         self.netG = networks.define_G(opt).to(self.device)
         self.netD = None
@@ -360,23 +394,17 @@ class VideoSRGANModel(_TrainingState):
         self.optimizers.append(self.optimizer_D)
         self._build_schedulers(train_opt, 'MultiStepLR')
         if self.dist:
-            bucket_mb = float(os.environ.get('RVSR_BUCKET_MB', train_opt.get('bucket_mb', 4.0)))
-            force = bool(train_opt.get('force_allreduce'))
-            self.reducer_G = BucketedGradAllReduce(None, bucket_mb=bucket_mb, buffers=self.optimizer_G.buffers, broadcast=False, force=force)
-            self.reducer_D = BucketedGradAllReduce(None, bucket_mb=bucket_mb, buffers=self.optimizer_D.buffers, broadcast=False, force=force)
-        self.log_dict = OrderedDict()
+            self.reducer_G = self._build_reducer(self.optimizer_G.buffers)
+            self.reducer_D = self._build_reducer(self.optimizer_D.buffers)
 
     # ------------------------------------------------------------------ data
     def feed_data(self, data, need_GT=True):
-        if 'GT_window' in data or data['LQs'].dtype == torch.uint8:   # packed crops of realvsr_amd.data (a packed 'ref' is not defined: the GT is the reference)
-            self.var_L, var_H = feed_packed(data, self.device, need_GT)
-            if need_GT:
-                self.var_H = self.var_ref = var_H
-            return
-        self.var_L = data['LQs'].to(self.device)
+        super().feed_data(data, need_GT)
         if need_GT:
-            self.var_H = data['GT'].to(self.device)
-            self.var_ref = (data['ref'] if 'ref' in data else data['GT']).to(self.device)
+            if _is_packed(data):   # (a packed 'ref' is not defined: the GT is the reference)
+                self.var_ref = self.var_H
+            else:
+                self.var_ref = (data['ref'] if 'ref' in data else data['GT']).to(self.device)
 
     # ------------------------------------------------------------------ one optimisation step
     def _set_requires_grad_D(self, flag):
@@ -388,17 +416,10 @@ class VideoSRGANModel(_TrainingState):
         from . import util
         # G
         self._set_requires_grad_D(False)
-        if self.reducer_G is not None:
-            self.reducer_G.zero_grad()
-        else:
-            self.optimizer_G.zero_grad()
-        aug = self.opt.get('augment')
-        if aug:
-            self.var_H, self.var_L = augments.apply_augment(self.var_H, self.var_L, aug['augs'], aug['probs'], aug['alphas'], aug['mix_p'])
+        self._zero_grad(self.optimizer_G, self.reducer_G)
+        self._augment()
         self.fake_H = self.netG(self.var_L)
-        c = self.var_L.size(1) // 2
-        gt = self.var_H[:, c] if self.var_H.dim() == 5 else self.var_H
-        ref = self.var_ref[:, c] if self.var_ref.dim() == 5 else self.var_ref
+        gt, ref = self._center_frame(self.var_H), self._center_frame(self.var_ref)
         fake_y, fake_c = self.fake_H[:, 0:1], self.fake_H[:, 1:3]
         real_y, real_c = gt[:, 0:1].contiguous(), gt[:, 1:3].contiguous()
         fake_pyr = util.laplacian_pyramid(img=fake_y, max_levels=3)
@@ -434,16 +455,11 @@ class VideoSRGANModel(_TrainingState):
             total = total + l_g_gan
             terms['l_g_total'] = total
             total.backward()
-            if self.reducer_G is not None:
-                self.reducer_G.finish()
-            self.optimizer_G.step()
+            self._finish_and_step(self.optimizer_G, self.reducer_G)
 
         # D
         self._set_requires_grad_D(True)
-        if self.reducer_D is not None:
-            self.reducer_D.zero_grad(passes=2)
-        else:
-            self.optimizer_D.zero_grad()
+        self._zero_grad(self.optimizer_D, self.reducer_D, passes=2)
         fake_in = [x.detach() for x in fake_pyr[:-1]]
         real_in = ref_pyr[:-1]
         l_d_real, l_d_fake = 0, 0
@@ -467,51 +483,20 @@ class VideoSRGANModel(_TrainingState):
             for i in range(len(pred_d_fake)):
                 l_d_fake = l_d_fake + self.cri_gan(pred_d_fake[i], False)
             l_d_fake.backward()
-        if self.reducer_D is not None:
-            self.reducer_D.finish()
-        self.optimizer_D.step()
+        self._finish_and_step(self.optimizer_D, self.reducer_D)
         terms['l_d_real'] = l_d_real.detach()
         terms['l_d_fake'] = l_d_fake.detach()
-        self.loss_terms = terms
-        if log:
-            for k, v in terms.items():
-                self.log_dict[k] = v.item()
-
-    def test(self):
-        self.netG.eval()
-        with torch.no_grad():
-            self.fake_H = self.netG(self.var_L)
-        self.netG.train()
+        self._keep_terms(terms, log)
 
     # ------------------------------------------------------------------ bookkeeping
-    def get_current_log(self):
-        return self.log_dict
-
-    def get_current_visuals(self, need_GT=True):
-        out = OrderedDict()
-        out['LQs'] = self.var_L.detach()[0].float().cpu()
-        out['HQ'] = self.fake_H.detach()[0].float().cpu()
-        if need_GT:
-            out['GT'] = self.var_H.detach()[0].float().cpu()
-        return out
-
-    def get_current_learning_rate(self):
-        return [g['lr'] for g in self.optimizers[0].param_groups]
-
     def load(self):
+        super().load()
         path = self.opt.get('path') or {}
-        strict = path.get('strict_load', True)
-        if path.get('pretrain_model_G') is not None:
-            VideoSRModel.load_network(self, path['pretrain_model_G'], self.netG, strict)
         if self.is_train and path.get('pretrain_model_D') is not None:
-            VideoSRModel.load_network(self, path['pretrain_model_D'], self.netD, strict)
+            self.load_network(path['pretrain_model_D'], self.netD, path.get('strict_load', True))
 
     def _networks_to_save(self):
         return [('G', self.netG), ('D', self.netD)]
-
-    load_network = VideoSRModel.load_network
-    save_network = VideoSRModel.save_network
-    get_current_metrics = VideoSRModel.get_current_metrics
 
 
 def create_model(opt):

@@ -134,6 +134,28 @@ def test_create_model_refuses_cpu_and_unknown_models():
         create_model(dict(opt, model='VideoSRGAN_AllPair_YCbCr_Split'))
 
 
+@pytest.mark.parametrize('name', ['VideoSR_AllPair_YCbCr_Split', 'VideoSR_AllPair_YCbCr_Combine', 'VideoSRGAN_AllPair_YCbCr_Split'])
+def test_every_model_gets_the_training_loops_methods_from_one_base(name, monkeypatch):
+    """What realvsr_amd.train calls exists on the class create_model picks, and the methods that do not depend on the losses are
+    defined once, in the base of both model classes: neither class carries its own copy or borrows the other's."""
+    from realvsr_amd import VideoSR_model as M
+    with pytest.raises(NotImplementedError, match='no CPU path'):
+        M.create_model({'model': name, 'gpu_ids': None})          # refused before any other key is read
+    for cls in (M.VideoSRModel, M.VideoSRGANModel):
+        monkeypatch.setattr(cls, '__init__', lambda self, *a, **k: None)
+    cls = type(M.create_model({'model': name}))
+    assert cls is (M.VideoSRGANModel if 'GAN' in name else M.VideoSRModel)
+    for method in ('resume_training', 'update_learning_rate', 'feed_data', 'optimize_parameters', 'get_current_learning_rate',
+                   'get_current_log', 'save', 'save_training_state', 'test', 'get_current_metrics', 'get_current_visuals'):
+        assert callable(getattr(cls, method)), method
+    shared = ('load_network', 'save_network', 'get_current_metrics', 'test', 'get_current_log', 'get_current_visuals',
+              'get_current_learning_rate')
+    for method in shared:
+        assert method not in M.VideoSRGANModel.__dict__ and method not in M.VideoSRModel.__dict__, method
+        owners = [c for c in cls.__mro__ if method in c.__dict__]
+        assert len(owners) == 1 and issubclass(M.VideoSRModel, owners[0]) and issubclass(M.VideoSRGANModel, owners[0]), method
+
+
 def test_flat_buffers_layout_and_guards():
     """optim.FlatBuffers: parameters and gradients become views of two identically laid-out buffers (CPU tensors are
     fine for the layout logic); re-binding a gradient is detected."""

@@ -29,21 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 FRAME_HW = (256, 448)
 
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def _event_ms(fn, inner):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for _ in range(inner):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / inner
+from step_timing import event_ms, median  # noqa: E402
 
 
 def _host_resize(img, scale_num, scale_den):
@@ -147,12 +133,12 @@ def measure(B, N, S, scale, mode_name, rounds, inner):
         _composed(win, scale, mode, h, S, w0)
     a, b = [], []
     for _ in range(rounds):
-        a.append(_event_ms(fused, inner))
-        b.append(_event_ms(lambda: _composed(win, scale, mode, h, S, w0), max(1, inner // 4)))
-    res['degrade_ms'], res['degrade_ms_min_max'] = round(_median(a), 5), [round(min(a), 5), round(max(a), 5)]
-    res['composed_ms'], res['composed_ms_min_max'] = round(_median(b), 5), [round(min(b), 5), round(max(b), 5)]
+        a.append(event_ms(fused, inner))
+        b.append(event_ms(lambda: _composed(win, scale, mode, h, S, w0), max(1, inner // 4)))
+    res['degrade_ms'], res['degrade_ms_min_max'] = round(median(a), 5), [round(min(a), 5), round(max(a), 5)]
+    res['composed_ms'], res['composed_ms_min_max'] = round(median(b), 5), [round(min(b), 5), round(max(b), 5)]
     res['bytes_moved'] = win.numel() + lq.numel() + gt.numel()
-    res['degrade_tbps'] = round(res['bytes_moved'] / (_median(a) * 1e-3) / 1e12, 4)
+    res['degrade_tbps'] = round(res['bytes_moved'] / (median(a) * 1e-3) / 1e12, 4)
     res['fused_below_composed_by_more_than_the_spread'] = bool(max(a) < min(b))
 
     frame = np.random.RandomState(5).randint(0, 256, FRAME_HW + (3,)).astype(np.uint8)
@@ -164,7 +150,7 @@ def measure(B, N, S, scale, mode_name, rounds, inner):
             x = _host_resize(x, scale, 1)
         ref_bytes = np.clip(np.round(255. * x.astype(np.float64)), 0, 255).astype(np.uint8)
         s.append((time.perf_counter() - t) * 1e3)
-    res['host_ref_ms_per_frame'] = round(_median(s), 2)
+    res['host_ref_ms_per_frame'] = round(median(s), 2)
     res['host_ref_differs_from_model'] = int((ref_bytes != br.degrade_frame(frame, scale, mode)).sum())
     return res
 

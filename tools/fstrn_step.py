@@ -24,18 +24,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-
-def _time_ms(fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
-    torch.cuda.synchronize()
-    ev[0].record()
-    for i in range(reps):
-        fn()
-        ev[i + 1].record()
-    torch.cuda.synchronize()
-    return sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(reps))
+from step_timing import clip_batch, lap_ms, median, split_opt, train_ms_step  # noqa: E402
 
 
 def tconv3_times(T, B, S, reps, rounds=2):
@@ -60,14 +49,13 @@ def tconv3_times(T, B, S, reps, rounds=2):
                 for fuse in (True, False):
                     RF._FUSE_TCONV3 = fuse
                     for name, fn in calls.items():
-                        samples.setdefault((('tconv3' if fuse else 'composed'), name), []).extend(_time_ms(fn, reps))
+                        samples.setdefault((('tconv3' if fuse else 'composed'), name), []).extend(lap_ms(fn, reps, 3))
     finally:
         RF._FUSE_TCONV3 = was
     out = {}
     for (kind, name), v in samples.items():
-        v = sorted(v)
-        out['%s_%s_ms' % (kind, name)] = round(v[len(v) // 2], 4)
-        out['%s_%s_ms_min_max' % (kind, name)] = [round(v[0], 4), round(v[-1], 4)]
+        out['%s_%s_ms' % (kind, name)] = round(median(v), 4)
+        out['%s_%s_ms_min_max' % (kind, name)] = [round(min(v), 4), round(max(v), 4)]
     tensor_gb = T * B * C * S * S * 4 / 1e9
     for name, passes in (('fwd', 4), ('dgrad', 2), ('wgrad', 2)):
         out['tconv3_%s_gbs' % name] = round(passes * tensor_gb / out['tconv3_%s_ms' % name] * 1e3, 1)
@@ -85,27 +73,13 @@ def main():
     a = ap.parse_args()
     from realvsr_amd.VideoSR_model import create_model
     torch.cuda.set_device(0)
-    opt = {'model': 'VideoSR_AllPair_YCbCr_Split', 'dist': False, 'gpu_ids': [0], 'is_train': True, 'scale': 1, 'augment': None,
-           'network_G': {'which_model_G': 'FSTRN', 'k': 3, 'nf': 64, 'nframes': 3},
-           'path': {}, 'train': {'pixel_criterion_y': 'lappyr', 'pixel_weight_y': 1.0, 'pixel_criterion_c': 'gw', 'pixel_weight_c': 1.0,
-                                 'weight_decay_G': 0, 'ft_tsa_only': 0, 'lr_G': 1e-4, 'beta1': 0.9, 'beta2': 0.99}}
+    opt = split_opt({'which_model_G': 'FSTRN', 'k': 3, 'nf': 64, 'nframes': 3})
     torch.manual_seed(0)
     model = create_model(opt)
-    g = torch.Generator(device='cuda').manual_seed(1)
     B, S = a.batch, a.size
-    data = {'LQs': torch.rand(B, 3, 3, S, S, device='cuda', generator=g), 'GT': torch.rand(B, 3, 3, S, S, device='cuda', generator=g)}
-    for step in range(1, a.warmup + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for step in range(a.warmup + 1, a.warmup + a.steps + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t1.record()
-    torch.cuda.synchronize()
-    res = {'metric': 'fstrn_step', 'batch': B, 'frames': 3, 'size': S, 'ms_step': round(t0.elapsed_time(t1) / a.steps, 2),
+    data = clip_batch(B, S, 1)
+    ms_step = train_ms_step(model, data, a.warmup, a.steps)
+    res = {'metric': 'fstrn_step', 'batch': B, 'frames': 3, 'size': S, 'ms_step': round(ms_step, 2),
            'loss_terms': {k: round(float(v), 5) for k, v in model.loss_terms.items()},
            'peak_mem_gb': round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
     del model, data

@@ -31,6 +31,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from step_timing import clip_batch  # noqa: E402
+
 
 def conv5_rates(B, reps=5):
     """(forward, weight gradient) TFLOP/s of two discriminator layers: 64 -> 64 at S/2 and 256 -> 256 at S/4."""
@@ -126,9 +128,8 @@ def main():
            'path': {}, 'train': train}
     torch.manual_seed(0 if rank == 0 else 12345 + rank)   # ranks > 0 start from different weights: the model broadcasts rank 0's
     model = create_model(opt)
-    g = torch.Generator(device='cuda').manual_seed(1 + rank)
     B, S = a.batch // world, a.size
-    data = {'LQs': torch.rand(B, 3, 3, S, S, device='cuda', generator=g), 'GT': torch.rand(B, 3, 3, S, S, device='cuda', generator=g)}
+    data = clip_batch(B, S, 1 + rank)
 
     # events where the model switches D's requires_grad: False = start of the G half, True = start of the D half
     marks = []

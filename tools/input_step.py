@@ -28,21 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def _event_ms(fn, inner):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for _ in range(inner):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / inner
+from step_timing import event_ms, median  # noqa: E402
 
 
 def _composed(u8, flags_host, out=None):
@@ -70,8 +56,8 @@ def _alternate(fused, composed, rounds, inner):
         composed()
     a, b = [], []
     for _ in range(rounds):
-        a.append(_event_ms(fused, inner))
-        b.append(_event_ms(composed, max(1, inner // 4)))
+        a.append(event_ms(fused, inner))
+        b.append(event_ms(composed, max(1, inner // 4)))
     return a, b
 
 
@@ -136,7 +122,7 @@ def measure(B, N, S, rounds, inner):
             t = time.perf_counter()
             fn()
             s.append((time.perf_counter() - t) * 1e3)
-        res[name + '_ms'] = round(_median(s), 3)
+        res[name + '_ms'] = round(median(s), 3)
         res[name + '_ms_min_max'] = [round(min(s), 3), round(max(s), 3)]
     res['h2d_bytes_ref'] = 2 * B * N * 3 * S * S * 4
     res['h2d_bytes_packed'] = 2 * B * N * 3 * S * S + 4 * B
@@ -146,9 +132,9 @@ def measure(B, N, S, rounds, inner):
         res[prefix + 'composed_equal'] = bool(torch.equal(data.assemble_batch(u8, flags), _composed(u8, flags_host)))
         res[prefix + 'composed_scalar_div_equal'] = bool(torch.equal(data.assemble_batch(u8, None, 0), u8.float().div(255.).permute(0, 1, 4, 2, 3)))
         a, b = _alternate(lambda: data.assemble_batch(u8, flags, out=out), lambda: _composed(u8, flags_host), rounds, inner)
-        res[prefix + 'assemble_ms'], res[prefix + 'assemble_ms_min_max'] = round(_median(a), 5), [round(min(a), 5), round(max(a), 5)]
-        res[prefix + 'composed_ms'], res[prefix + 'composed_ms_min_max'] = round(_median(b), 5), [round(min(b), 5), round(max(b), 5)]
-        res[prefix + 'assemble_tbps'] = round(u8.numel() * 5 / (_median(a) * 1e-3) / 1e12, 3)
+        res[prefix + 'assemble_ms'], res[prefix + 'assemble_ms_min_max'] = round(median(a), 5), [round(min(a), 5), round(max(a), 5)]
+        res[prefix + 'composed_ms'], res[prefix + 'composed_ms_min_max'] = round(median(b), 5), [round(min(b), 5), round(max(b), 5)]
+        res[prefix + 'assemble_tbps'] = round(u8.numel() * 5 / (median(a) * 1e-3) / 1e12, 3)
         res[prefix + 'fused_below_composed_by_more_than_the_spread'] = bool(max(a) < min(b))
 
     lq, _, flags = stager._views(stager._dev[0])

@@ -21,18 +21,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-
-def _median_ms(fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
-    torch.cuda.synchronize()
-    ev[0].record()
-    for i in range(reps):
-        fn()
-        ev[i + 1].record()
-    torch.cuda.synchronize()
-    return sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(reps))[reps // 2]
+from step_timing import clip_batch, lap_ms, median, split_opt, train_ms_step  # noqa: E402
 
 
 def ca_times(B, S, reps):
@@ -57,14 +46,14 @@ def ca_times(B, S, reps):
     passes = 4 * B * C * S * S * 4 / 1e9   # GB moved at 4 passes over one f32 tensor
     for name, fn in (('ca', fused), ('composed', composed)):
         with torch.no_grad():
-            fwd = _median_ms(fn, reps)
+            fwd = median(lap_ms(fn, reps, 3))
         y = fn()
 
         def bwd():
             for t in (u, x, down.weight, down.bias, up.weight, up.bias):
                 t.grad = None
             y.backward(gout, retain_graph=True)
-        out[name + '_fwd_ms'], out[name + '_bwd_ms'] = round(fwd, 4), round(_median_ms(bwd, reps), 4)
+        out[name + '_fwd_ms'], out[name + '_bwd_ms'] = round(fwd, 4), round(median(lap_ms(bwd, reps, 3)), 4)
         del y
     out['ca_fwd_gbs'], out['ca_bwd_gbs'] = round(passes / out['ca_fwd_ms'] * 1e3, 1), round(passes / out['ca_bwd_ms'] * 1e3, 1)
     return out
@@ -80,28 +69,14 @@ def main():
     a = ap.parse_args()
     from realvsr_amd.VideoSR_model import create_model
     torch.cuda.set_device(0)
-    opt = {'model': 'VideoSR_AllPair_YCbCr_Split', 'dist': False, 'gpu_ids': [0], 'is_train': True, 'scale': 1, 'augment': None,
-           'network_G': {'which_model_G': 'RCAN', 'num_in_ch': 3, 'num_out_ch': 3, 'num_frames': 3, 'num_feat': 64, 'num_group': 5,
-                         'num_block': 2, 'squeeze_factor': 16, 'res_scale': 1},
-           'path': {}, 'train': {'pixel_criterion_y': 'lappyr', 'pixel_weight_y': 1.0, 'pixel_criterion_c': 'gw', 'pixel_weight_c': 1.0,
-                                 'weight_decay_G': 0, 'ft_tsa_only': 0, 'lr_G': 1e-4, 'beta1': 0.9, 'beta2': 0.99}}
+    opt = split_opt({'which_model_G': 'RCAN', 'num_in_ch': 3, 'num_out_ch': 3, 'num_frames': 3, 'num_feat': 64, 'num_group': 5,
+                     'num_block': 2, 'squeeze_factor': 16, 'res_scale': 1})
     torch.manual_seed(0)
     model = create_model(opt)
-    g = torch.Generator(device='cuda').manual_seed(1)
     B, S = a.batch, a.size
-    data = {'LQs': torch.rand(B, 3, 3, S, S, device='cuda', generator=g), 'GT': torch.rand(B, 3, 3, S, S, device='cuda', generator=g)}
-    for step in range(1, a.warmup + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for step in range(a.warmup + 1, a.warmup + a.steps + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t1.record()
-    torch.cuda.synchronize()
-    res = {'metric': 'rcan_step', 'batch': B, 'frames': 3, 'size': S, 'ms_step': round(t0.elapsed_time(t1) / a.steps, 2),
+    data = clip_batch(B, S, 1)
+    ms_step = train_ms_step(model, data, a.warmup, a.steps)
+    res = {'metric': 'rcan_step', 'batch': B, 'frames': 3, 'size': S, 'ms_step': round(ms_step, 2),
            'loss_terms': {k: round(float(v), 5) for k, v in model.loss_terms.items()}}
     del model, data
     torch.cuda.empty_cache()

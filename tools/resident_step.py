@@ -34,23 +34,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
+from step_timing import event_ms, median  # noqa: E402
+
 H, W, C = 1024, 512, 3
-
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def _event_ms(fn, inner):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for _ in range(inner):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / inner
 
 
 def _host_numbers(res, load_frames, workers, device='cuda'):
@@ -71,7 +57,7 @@ def _host_numbers(res, load_frames, workers, device='cuda'):
                 t = time.perf_counter()
                 np.ascontiguousarray(data._read_png_u8(path))
                 s.append((time.perf_counter() - t) * 1e3)
-            res['png_decode_ms_per_frame' if name == 'noise' else 'png_decode_smooth_ms_per_frame'] = round(_median(s), 3)
+            res['png_decode_ms_per_frame' if name == 'noise' else 'png_decode_smooth_ms_per_frame'] = round(median(s), 3)
         per_seq = 50
         sequences = tuple('%03d' % i for i in range(max(1, load_frames // per_seq)))
         tree = os.path.join(tmp, 'tree')
@@ -143,13 +129,13 @@ def measure(a):
         gather(), composed(), assemble()
     s = {'gather': [], 'composed': [], 'assemble': []}
     for _ in range(a.rounds):
-        s['gather'].append(_event_ms(gather, a.inner))
-        s['composed'].append(_event_ms(composed, max(1, a.inner // 4)))
-        s['assemble'].append(_event_ms(assemble, a.inner))
+        s['gather'].append(event_ms(gather, a.inner))
+        s['composed'].append(event_ms(composed, max(1, a.inner // 4)))
+        s['assemble'].append(event_ms(assemble, a.inner))
     for name, v in s.items():
-        res[name + '_ms'], res[name + '_ms_min_max'] = round(_median(v), 5), [round(min(v), 5), round(max(v), 5)]
-    res['gather_tbps'] = round(B * N * S * S * C * 5 / (_median(s['gather']) * 1e-3) / 1e12, 3)
-    res['gather_over_assemble'] = round(_median(s['gather']) / _median(s['assemble']), 3)
+        res[name + '_ms'], res[name + '_ms_min_max'] = round(median(v), 5), [round(min(v), 5), round(max(v), 5)]
+    res['gather_tbps'] = round(B * N * S * S * C * 5 / (median(s['gather']) * 1e-3) / 1e12, 3)
+    res['gather_over_assemble'] = round(median(s['gather']) / median(s['assemble']), 3)
     res['gather_below_composed_by_more_than_the_spread'] = bool(max(s['gather']) < min(s['composed']))
     res['table_h2d_bytes'] = B * (N + 3) * 4
     return res

@@ -25,21 +25,10 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from step_timing import clip_batch, lap_ms, median, split_opt, train_ms_step  # noqa: E402
+
 SPYNET_LAYERS = [(6, 32), (8, 32), (32, 64), (64, 32), (32, 16), (16, 2)]
 
-
-def _median_ms(fn, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
-    torch.cuda.synchronize()
-    ev[0].record()
-    for i in range(reps):
-        fn()
-        ev[i + 1].record()
-    torch.cuda.synchronize()
-    v = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(reps))
-    return v[len(v) // 2]
 
 
 def conv7_times(B, S, reps):
@@ -58,7 +47,7 @@ def conv7_times(B, S, reps):
         for name, fn in (('fwd', lambda: RF._conv(x, w, y, bias=b, what='conv7 fwd')),
                          ('dgrad', lambda: RF._conv(gout, w, gx, transposed=True, what='conv7 dgrad')),
                          ('wgrad', lambda: RF._conv_wgrad(x, gout, gw, gb, what='conv7 wgrad'))):
-            ms = _median_ms(fn, reps)
+            ms = median(lap_ms(fn, reps, 2))
             row[name + '_ms'], row[name + '_tflops'] = round(ms, 3), round(tflop / ms * 1e3, 1)
         out['%dto%d' % (C, Co)] = row
         del x, gout, y, gx
@@ -81,8 +70,8 @@ def resample_times(B, S, K, reps):
                            ('upsample', lambda: RF.upsample2_ac(small, 2.0))):
             y = make()
             gy = torch.randn_like(y)
-            fwd = _median_ms(make, reps)
-            bwd = _median_ms(lambda: y.backward(gy, retain_graph=True), reps)
+            fwd = median(lap_ms(make, reps, 2))
+            bwd = median(lap_ms(lambda: y.backward(gy, retain_graph=True), reps, 2))
             res[name] = (fwd, bwd)
         return res
 
@@ -112,7 +101,7 @@ def halves(model, B, S, reps):
         net.zero_grad(set_to_none=True)
         net.sr_arch(clip).sum().backward()
 
-    return {'spynet_ms': round(_median_ms(spynet, reps, 1), 2), 'sr_ms': round(_median_ms(sr, reps, 1), 2)}
+    return {'spynet_ms': round(median(lap_ms(spynet, reps, 1)), 2), 'sr_ms': round(median(lap_ms(sr, reps, 1)), 2)}
 
 
 def main():
@@ -127,28 +116,14 @@ def main():
     from realvsr_amd.VideoSR_model import create_model
     torch.cuda.set_device(0)
     K = 3
-    opt = {'model': 'VideoSR_AllPair_YCbCr_Split', 'dist': False, 'gpu_ids': [0], 'is_train': True, 'scale': 1, 'augment': None,
-           'network_G': {'which_model_G': 'TOF', 'nframes': 3, 'K': K, 'nc': 3, 'nf': 64, 'nb': 10},
-           'path': {}, 'train': {'pixel_criterion_y': 'lappyr', 'pixel_weight_y': 1.0, 'pixel_criterion_c': 'gw', 'pixel_weight_c': 1.0,
-                                 'weight_decay_G': 0, 'ft_tsa_only': 0, 'lr_G': 1e-4, 'beta1': 0.9, 'beta2': 0.99}}
+    opt = split_opt({'which_model_G': 'TOF', 'nframes': 3, 'K': K, 'nc': 3, 'nf': 64, 'nb': 10})
     torch.manual_seed(0)
     model = create_model(opt)
-    g = torch.Generator(device='cuda').manual_seed(1)
     B, S = a.batch, a.size
-    data = {'LQs': torch.rand(B, 3, 3, S, S, device='cuda', generator=g), 'GT': torch.rand(B, 3, 3, S, S, device='cuda', generator=g)}
-    for step in range(1, a.warmup + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0.record()
-    for step in range(a.warmup + 1, a.warmup + a.steps + 1):
-        model.feed_data(data)
-        model.optimize_parameters(step, log=False)
-    t1.record()
-    torch.cuda.synchronize()
+    data = clip_batch(B, S, 1)
+    ms_step = train_ms_step(model, data, a.warmup, a.steps)
     res = {'metric': 'tof_step', 'gemm_mode': _lib.get_gemm_mode(), 'batch': B, 'frames': 3, 'size': S, 'K': K,
-           'ms_step': round(t0.elapsed_time(t1) / a.steps, 2),
+           'ms_step': round(ms_step, 2),
            'loss_terms': {k: round(float(v), 5) for k, v in model.loss_terms.items()},
            'peak_mem_gb': round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
     del data
