@@ -260,7 +260,8 @@ int rvsr_deform_conv_generic_backward(int dtype, const void* input, const void* 
  *               Activations must lie inside f16's range (|x| < 65504; below 6e-8 they round to zero).  A packed image (w_mode | 2) must
  *               have been written with the same flag.  realvsr_amd.set_gemm_mode('f16fp8') sets it on every eligible forward conv.
  *   out1 (B,Co1,Hout,Wout) [+ out2 (B,Co2,Hout,Wout): rows split, for the gradient of a cat].
- *   residual (NULL or shaped like out1, out2 must be NULL): added after the activation.
+ *   residual (NULL or shaped like out1, out2 must be NULL): added after the activation.  It may be out1 itself (in-place accumulation):
+ *        every element is read before it is stored, by the lane that stores it; act 3 reads `residual` as a mask and must not alias.
  *   act: 0 none, 1 ReLU, 2 LeakyReLU(slope); 3 (with `residual`, ksize 3, stride 1, one output): out = (conv + bias) * (residual > 0 ? 1 : slope),
  *        i.e. a data gradient multiplied by the derivative of the activation whose saved OUTPUT `residual` is -- the consumers of that
  *        gradient then need no mask.  An epilogue of the 8 x 64-tile kernel only: for calls that kernel does not take the plan refuses

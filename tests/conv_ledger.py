@@ -212,6 +212,72 @@ def conv5_calls(case):
     return calls_of((C, 0, Co, 5, stride, act, False, False, B, H, W))
 
 
+def conv3d_frames_calls(case, need_x=True, need_w=True):
+    """The calls of functional.conv3d_frames for (T, f0, f1, B, Ci, Co, H, W, k, bias, residual), forward and backward: one 2-D conv per
+    temporal tap over the frame range it meets (functional._c3_taps: the centre tap first, the outer taps accumulate in place), the same
+    for the data gradient, one weight gradient per tap.  x, the residual and the output gradient are aligned tensors; a frame range
+    starts a whole number of frames in.  need_w: the weight or the bias wants a gradient."""
+    from realvsr_amd.functional import _c3_taps
+    T, f0, f1, B, Ci, Co, H, W, k, _, use_res = case
+    taps = _c3_taps(T, f0, f1)
+    xo = lambda a: (a * B * Ci * H * W) % 4    # noqa: E731  (float offset of input frame a)
+    yo = lambda o: (o * B * Co * H * W) % 4    # noqa: E731  (of output frame o)
+    calls = []
+    for i, (dt, a, n, o) in enumerate(taps):
+        calls.append(('tap %d' % dt, fwd_call(Ci, Co, H, W, H, W, n * B, k=k, res=use_res if i == 0 else True, x_off=xo(a), out_off=yo(o),
+                                              res_off=0 if i == 0 else yo(o))))
+    if need_x:
+        for i, (dt, a, n, o) in enumerate(taps):
+            calls.append(('dgrad tap %d' % dt, fwd_call(Co, Ci, H, W, H, W, n * B, k=k, w_mode=1, res=i > 0, x_off=yo(o), out_off=xo(a),
+                                                        res_off=xo(a))))
+    if need_w:
+        for dt, a, n, o in taps:
+            calls.append(('wgrad tap %d' % dt, wgrad_call(Ci, Co, H, W, H, W, n * B, k=k, x_off=xo(a), g_off=yo(o))))
+    return calls
+
+
+def tsa_block_calls(case, need_aligned=True, need_1=True, need_2=True):
+    """The calls of functional.tsa_temporal_block for (N, center, B, C, H, W): tAtt_1 on all N * B frames, tAtt_2 on the centre block,
+    their weight gradients, and the two data gradients that accumulate in place into the gradient of `aligned` and its centre block."""
+    N, center, B, C, H, W = case
+    coff = (center * B * C * H * W) % 4
+    calls = [('tAtt_1', fwd_call(C, C, H, W, H, W, N * B)), ('tAtt_2', fwd_call(C, C, H, W, H, W, B, x_off=coff))]
+    if need_1:
+        calls.append(('wgrad tAtt_1', wgrad_call(C, C, H, W, H, W, N * B)))
+    if need_2:
+        calls.append(('wgrad tAtt_2', wgrad_call(C, C, H, W, H, W, B, x_off=coff)))
+    if need_aligned:
+        calls.append(('dgrad tAtt_1', fwd_call(C, C, H, W, H, W, N * B, w_mode=1, res=True)))
+        calls.append(('dgrad tAtt_2', fwd_call(C, C, H, W, H, W, B, w_mode=1, res=True, res_off=coff, out_off=coff)))
+    return calls
+
+
+def conv_transpose1x1_calls(case):
+    """The calls of functional.conv_transpose1x1 for (batch, Ci, Co, H, W): the forward is a transposed-weight 1x1 conv, its data
+    gradient a plain one, the weight gradient that of a Ci -> Co conv (copied back through a transpose)."""
+    Bn, Ci, Co, H, W = case
+    return [('forward', fwd_call(Ci, Co, H, W, H, W, Bn, k=1, w_mode=1)), ('dgrad', fwd_call(Co, Ci, H, W, H, W, Bn, k=1)),
+            ('wgrad', wgrad_call(Ci, Co, H, W, H, W, Bn, k=1))]
+
+
+def inplace_call(case):
+    """The functional._conv call of an in-place case of tests/test_gpu_conv_inplace.py: (C1, C2, Co, k, stride, transposed, xact, B, H,
+    W, x_off, out_off); the residual IS the output buffer, so it shares the output's offset."""
+    C1, C2, Co, k, stride, transposed, xact, B, H, W, x_off, out_off = case
+    Ho, Wo = out_size(H, W, k, stride)
+    return fwd_call(C1, Co, H, W, Ho, Wo, B, k=k, stride=stride, C2=C2, xact=xact, res=True, w_mode=1 if transposed else 0, x_off=x_off,
+                    x2_off=x_off, xact_off=x_off, res_off=out_off, out_off=out_off)
+
+
+def residual_epilogue_key(call, row):
+    """A kernel variant that can carry a residual: the forward kernel, whether it stores 16 bytes at a time, and whether the output or
+    the residual is off a 16-byte boundary.  None for a call without a residual or with the mask epilogue (which reads `residual` as a
+    mask and never aliases)."""
+    if not call['res'] or call['act'] == ACT_MASK:
+        return None
+    return (fwd_kernel_key(call, row), row['vec4'], bool(call['out_off'] or call['res_off']))
+
+
 # ---- ledger keys
 def fwd_kernel_key(call, row):
     return (FWD_FAMILY[row['family']], call['k'], call['stride'], row['MT'], row['vec'], row['wide'], row['NT'], row['act_in'])

@@ -86,7 +86,41 @@ def _universe(mode, only=None):
             got = CL.collect(CL.conv5_calls(case), mode, got)
         # (act' on a strided or 5x5 forward conv has no caller in functional.py: the raw-ABI cases are its call space)
         got = CL.collect(RAW_LEDGER_CALLS, mode, got)
+        got = CL.collect(_frame_node_calls(), mode, got)
     return got
+
+
+_frame_calls = []
+
+
+def _frame_node_calls():
+    """The distinct calls of the frame-major nodes built from plain conv calls -- conv3d_frames, tsa_temporal_block,
+    conv_transpose1x1 -- over their call space: T 1..5 with every frame range, N 1..7 with the centre first, middle and last, the
+    channel counts of FSTRN and EDVR, frames from 5 x 7 to 8 x 64.  (They add no key: a node that starts issuing another call shows up
+    as an unreached one.)"""
+    if _frame_calls:
+        return _frame_calls
+    seen = set()
+
+    def add(node, case, calls):
+        for name, call in calls:
+            if tuple(call.values()) not in seen:
+                seen.add(tuple(call.values()))
+                _frame_calls.append(('%s %s %s' % (node, _name(case), name), call))
+    frames = ((5, 7), (8, 12), (9, 33), (8, 64))
+    for (H, W), B in itertools.product(frames, (1, 2)):
+        for Ci, Co in itertools.product((3, 16, 24, 32, 64), repeat=2):
+            for T in range(1, 6):
+                for f0, f1 in ((a, b) for a in range(T) for b in range(a + 1, T + 1)):
+                    case = (T, f0, f1, B, Ci, Co, H, W, 3, True, False)
+                    add('conv3d_frames', case, CL.conv3d_frames_calls(case))
+            case = (3, 0, 3, B, Ci, Co, H, W, 1, True, True)
+            add('conv3d_frames', case, CL.conv3d_frames_calls(case))
+            add('conv_transpose1x1', (3 * B, Ci, Co, H, W), CL.conv_transpose1x1_calls((3 * B, Ci, Co, H, W)))
+        for C, N in itertools.product((3, 16, 64), range(1, 8)):
+            for center in sorted({0, N // 2, N - 1}):
+                add('tsa_temporal_block', (N, center, B, C, H, W), CL.tsa_block_calls((N, center, B, C, H, W)))
+    return _frame_calls
 
 
 def _name(case):
@@ -197,6 +231,55 @@ def test_a_dropped_case_is_named():
         print('%-90s %s' % (name, [k for m in lost.values() for keys in m.values() for k in keys][:2]))
     lost = _missing(universe['bf16x3'], _reached('bf16x3', drop=nodes))
     assert ('fwd5', 3, 1, 1, 'mask', 1) in lost['forward epilogue'], lost
+
+
+# ---- residual == out1: every kernel variant that can carry a residual runs once in place (tests/test_gpu_conv_inplace.py)
+def _residual_universe(mode):
+    """{key: first call that gives it} over every call of the sweep above that carries a residual (the mask epilogue apart)."""
+    got = {}
+
+    def add(named_calls):
+        for name, call in named_calls:
+            if 'Gh' in call or not call['res'] or call['act'] == CL.ACT_MASK:
+                continue
+            rc, row = CL.fwd_plan(call, mode)
+            assert rc == 0, (call, rc)
+            got.setdefault(CL.residual_epilogue_key(call, row), call)
+    for case in _sweep_cases():
+        for (x_off, g_off), out_off in itertools.product(((0, 0), (1, 0), (0, 1), (1, 1)), (0, 1)):
+            calls = CL.calls_of(case, (x_off, x_off, g_off, out_off), mode)
+            add(calls)
+            if out_off:
+                add(_raw_variants(calls))
+    for node in _mask_nodes():
+        add(_node_calls(node, mode))
+    return got
+
+
+# key -> why no in-place case reaches it; at most 5 %
+INPLACE_EXEMPT = {'bf16x3': {}, 'f32': {}}
+
+
+@pytest.mark.parametrize('mode', ['bf16x3', 'f32'])
+def test_every_residual_epilogue_runs_in_place(mode):
+    """(forward kernel, 16-byte stores, output / residual off the boundary) of every residual-carrying call of the sweep is the key of
+    an INPLACE_CASES entry, which test_gpu_conv_inplace.py runs with the residual being the output buffer."""
+    from test_gpu_conv_inplace import INPLACE_CASES
+    universe = _residual_universe(mode)
+    reached = {}
+    for case in INPLACE_CASES:
+        call = CL.inplace_call(case)
+        rc, row = CL.fwd_plan(call, mode)
+        assert rc == 0, (case, rc)
+        reached.setdefault(CL.residual_epilogue_key(call, row), case)
+    exempt = INPLACE_EXEMPT[mode]
+    print('\nresidual epilogues that run in place, %s: %d keys' % (mode, len(universe)))
+    for key in sorted(universe, key=repr):
+        print('  %-70s %s' % (key, reached.get(key, 'EXEMPT: ' + exempt[key] if key in exempt else '-- NOT REACHED --')))
+    assert len(universe) >= 20   # (46 in bf16x3 mode, 21 in f32 mode when this was written)
+    assert len(exempt) <= 0.05 * len(universe) and all(k in universe for k in exempt)
+    missing = sorted((k for k in universe if k not in reached and k not in exempt), key=repr)
+    assert not missing, 'no in-place case reaches: %s' % missing
 
 
 def test_the_frames_of_the_mask_epilogue():

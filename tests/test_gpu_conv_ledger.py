@@ -185,4 +185,26 @@ def test_the_ledger_knows_the_calls_of_functional():
                                   ref_block=ref_sink or 0)
             y.backward(torch.randn_like(y))
         _same_calls('conv_cat_bcast %s' % (case,), rec.calls, CL.cat_bcast_calls(case))
+    # the frame-major nodes: 105-float frames, so that the frame ranges and the centre block start off a 16-byte boundary
+    for case in ((5, 1, 4, 1, 3, 16, 5, 7, 3, True, True), (2, 0, 2, 1, 16, 3, 5, 7, 3, True, False)):
+        T, f0, f1, B, Ci, Co, H, W, k, _, use_res = case
+        conv = nn.Conv3d(Ci, Co, (3, k, k), padding=(1, k // 2, k // 2)).to(d)
+        x = torch.randn(T, B, Ci, H, W, device=d, requires_grad=True)
+        res = torch.randn(f1 - f0, B, Co, H, W, device=d) if use_res else None
+        with _Recorder() as rec:
+            RF.conv3d_frames(x, conv, frames=(f0, f1), residual=res).backward(torch.randn(f1 - f0, B, Co, H, W, device=d))
+        _same_calls('conv3d_frames %s' % (case,), rec.calls, CL.conv3d_frames_calls(case))
+    case = (3, 1, 1, 3, 5, 7)
+    N, center, B, C, H, W = case
+    t1, t2 = nn.Conv2d(C, C, 3, 1, 1).to(d), nn.Conv2d(C, C, 3, 1, 1).to(d)
+    aligned = torch.randn(N, B, C, H, W, device=d, requires_grad=True)
+    with _Recorder() as rec:
+        RF.tsa_temporal_block(aligned, center, t1, t2).backward(torch.randn(B, N * C, H, W, device=d))
+    _same_calls('tsa_temporal_block %s' % (case,), rec.calls, CL.tsa_block_calls(case))
+    case = (6, 16, 24, 5, 7)
+    convt = nn.ConvTranspose3d(16, 24, 1).to(d)
+    x = torch.randn(3, 2, 16, 5, 7, device=d, requires_grad=True)
+    with _Recorder() as rec:
+        RF.conv_transpose1x1(x, convt).backward(torch.randn(3, 2, 24, 5, 7, device=d))
+    _same_calls('conv_transpose1x1 %s' % (case,), rec.calls, CL.conv_transpose1x1_calls(case))
     torch.cuda.synchronize()
