@@ -63,7 +63,14 @@ const char* rvsr_last_error(void);
  *   (which DCN calls these kernels take: dcn_fwd_plan / dcn_bwd_plan, csrc/dcn_plan.h; rvsr_dcn_pack_*_plan report the term count of a call).
  * Every other kernel (1x1 and strided forward convs and their weight gradients, narrow m-blocks such as the 3-channel output conv,
  * scalar-staged views, the generic DCN path of section 1c) computes three terms in modes 2 / 3, so a network off those shapes gets
- * mode 0's result and speed.  Other values select 0.  Process-wide switch. */
+ * mode 0's result and speed.  A gradient is a call of its own and its own plan decides: the data gradient of a stride-2 conv or of a
+ * conv with few output channels is a stride-1 conv_fwd5 call with the conv's INPUT channels as rows (64-row m-blocks from 33 input
+ * channels on: reduced), and conv_wgrad2 takes the weight gradient of every 3x3 stride-1 conv with more than 4 output channels (16-byte aligned, W % 4 == 0).
+ * The definition holds bit for bit for every output but the DCN's grad_input, an atomic scatter: there mode 2 / 3 differs from mode 0 on
+ * the rounded operands by the summation order alone, as two runs of mode 0 do (the fixed-point scale of dcn_bwdin6's window is taken
+ * from the rounded operands in these modes).  The DCN weight-gradient kernels form grad_bias as a product with a ones column, so it
+ * follows the rounded output gradient; the conv weight-gradient kernels sum the f32 output gradient and give mode 0's grad_bias.
+ * tests/test_gpu_modes_definition.py pins all of this per kernel.  Other values select 0.  Process-wide switch. */
 void rvsr_set_gemm_mode(int mode);
 int rvsr_get_gemm_mode(void);   /* the mode the CALLING thread's next call computes in */
 /* The same choice for the calling host thread only (every entry point reads the mode at call time on the calling thread): mode 0-3

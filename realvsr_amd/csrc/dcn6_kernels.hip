@@ -15,7 +15,8 @@
 //     bit-reproducible whatever the order.
 //     Scale: a contribution is w_corner * mask * col_grad with w, mask in [0, 1] and |col_grad[t, c, px]| = |<W[:, c, t], gOut[:, px]>|
 //     <= ||W[:, c, t]||_2 * ||gOut[:, px]||_2 (Cauchy-Schwarz); with Wn = the largest column norm of the chunk (dcn_bwd5_wnorm_kernel) and
-//     Gn = the largest pixel norm of the tile (prologue), S = 2^31 / (2304 * Wn * Gn) maps every contribution to |q| <= 2^19.8 and a cell
+//     Gn = the largest pixel norm of the tile (prologue) -- of the operands the products see: in the reduced-term GEMM modes the bf16-rounded
+//     weights and, with one term, the bf16-rounded output gradient --, S = 2^31 / (2304 * Wn * Gn) maps every contribution to |q| <= 2^19.8 and a cell
 //     can receive at most 8 * 32 * 9 = 2304 of them per chunk (each (pixel, tap) at most once): NO overflow for any input.
 //     One unit is ~1e-6 of the bound, round-to-nearest (magic-number add), so the quantisation noise of a cell (~6 units at 36
 //     contributions) stays below the bf16x3 error of col_grad itself; measured against the f64 oracle in tests/test_gpu_dcn*.py.
@@ -70,15 +71,19 @@ __host__ __device__ __forceinline__ int bwd6_tap(int it, int h) {
 }
 
 // Wn[chunk] for the fixed-point scale: one block per chunk, 576 threads = 72 (tap, channel) columns x 8 slices of the output
-// channels; slice sums combined through LDS, then the maximum over the columns
-__global__ __launch_bounds__(576) void dcn_bwd5_wnorm_kernel(const float* __restrict__ w, float* __restrict__ wn, int Co, int C) {
+// channels; slice sums combined through LDS, then the maximum over the columns.
+// hi_only (the reduced-term GEMM modes): the norms of the bf16-rounded weights, the operand those products see -- the scale, and with it
+// every fixed-point contribution, is then the one the three-term kernel derives from pre-rounded weights: a speed mode differs from mode 0
+// on the rounded operands by the summation order of the scatter alone (tests/test_gpu_modes_definition.py).
+__global__ __launch_bounds__(576) void dcn_bwd5_wnorm_kernel(const float* __restrict__ w, float* __restrict__ wn, int Co, int C, int hi_only) {
     __shared__ float red[576];
     const int chunk = blockIdx.x, t = threadIdx.x, col = t % 72, sl = t / 72;
     const int tap = col >> 3, c = 8 * chunk + (col & 7);
     float s = 0.f;
     if (c < C)
         for (int o = sl; o < Co; o += 8) {
-            const float v = w[((size_t)o * C + c) * 9 + tap];
+            float v = w[((size_t)o * C + c) * 9 + tap];
+            if (hi_only) v = (float)(__bf16)v;   // (round to nearest even: split8's hi part)
             s += v * v;
         }
     red[t] = s;
@@ -296,9 +301,13 @@ __global__ __launch_bounds__(512, WPS) void dcn_bwdin6_kernel(const DcnBwdIn6Par
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (px_ok && ol0 + j < d.Co) ? v[j] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gsq = __builtin_fmaf(v[j], v[j], gsq);
         split8(v, gh[ks], gl[ks]);
+        // (one term: the products see the rounded output gradient, and so does the scale -- see dcn_bwd5_wnorm_kernel)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float u = TERMS == 1 ? (float)gh[ks][j] : v[j];
+            gsq = __builtin_fmaf(u, u, gsq);
+        }
     }
     {   // Gn^2 = the largest squared pixel norm of the tile (read back after the first barrier)
         gsq = half_sum6(gsq);
@@ -715,7 +724,7 @@ int rvsr_launch_dcn_bwdin6(const DcnGeom& d, const DcnBwdPlan& q, const float* w
     const int nchunks = (d.C + 7) / 8;
     bf16x8* wpack = (bf16x8*)workspace;
     float* wnorm = (float*)((unsigned char*)workspace + lay.wnorm);
-    hipLaunchKernelGGL(dcn_bwd5_wnorm_kernel, dim3(nchunks), dim3(576), 0, st, weight, wnorm, d.Co, d.C);
+    hipLaunchKernelGGL(dcn_bwd5_wnorm_kernel, dim3(nchunks), dim3(576), 0, st, weight, wnorm, d.Co, d.C, q.in_nt < 3 ? 1 : 0);
     const size_t total = (size_t)nchunks * 3 * (2 * q.nk) * 32;
     const dim3 pg((unsigned)((total + 255) / 256)), pb(256);
     switch (q.nk) {

@@ -11,7 +11,7 @@ ACT = {'none': 0, 'relu': 1, 'lrelu': 2}
 ACT_MASK = 3
 GEMM = {'bf16x3': 0, 'f32': 1, 'bf16x2': 2, 'bf16': 3, 'f16fp8': 0}
 FWD_FAMILY = ('thin', 'fwd5', 'fwd2', 'f32')
-WGRAD_FAMILY = ('thin', 'wgrad2', 'wgrad5', 'f32_5', '1x1s', '1x1', 'f32_3s1', 's2', 'f32_3s2', 'f32_1')
+WGRAD_FAMILY = ('thin', 'wgrad2', 'wgrad5', 'f32_5', '1x1s', '1x1', 'f32_3s1', 's2', 'f32_3s2', 'f32_1', 'f32_7')
 _A = 0x10000000   # 16-byte aligned; the plans dereference nothing
 
 _FWD_KEYS = ('C1', 'C2', 'xact', 'in_mode', 'Hs', 'Ws', 'res', 'Co1', 'Co2', 'B', 'k', 'stride', 'w_mode', 'act', 'ps', 'Hout', 'Wout',

@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 
 ACT = {'none': 0, 'relu': 1, 'lrelu': 2}
-GEMM = {'bf16x3': 0, 'f32': 1}
+GEMM = {'bf16x3': 0, 'f32': 1, 'bf16x2': 2, 'bf16': 3}   # (the speed modes: tests/test_gpu_modes_definition.py asks for their term counts)
 FWD_FAMILY = ('dcn_fwd3', 'dcn_fwd2', 'dcn_fwd1')
 IN_FAMILY = ('none', 'dcn_bwdin6', 'dcn_bwd_input')
 W_FAMILY = ('none', 'dcn_bwdw6', 'dcn_bwdw4', 'dcn_bwdw2', 'dcn_bwd_weight')
